@@ -3,19 +3,29 @@
 workload configs[1]: Market-1501 ResNet-50 PPS, 1xMI355X, batch 64,
 3368q x 15913g L2 distmat).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one batch of 64 synthetic Market-sized images (uint8 BGR 128x64,
 resident in HBM) through the whole feature path: preprocess (mean-subtract +
 bicubic to 384x128) -> ResNet-50/stride-1 res5 -> part power set -> 31 heads
 -> L2 normalise.  value = images/s over all ranks (weak scaling: 64 per rank
-per step).  The retrieval stage (distance matrix + count-based mAP/CMC at
-Market sizes; gallery-sharded across ranks with an all-gather of queries) is
-timed after the step loop and reported as distmat_GBps etc.
+per step).
+
+A plain run does what `value` needs and nothing else: build the seeded model,
+tune its table, warm up, time K steps, write the last step's features if
+--dump-outputs is given, print the line.  --full adds every other
+measurement after the step loop: the PCIe-inclusive rate, the conv / distance
+/ rank / argsort rooflines, the retrieval stage (distance matrix +
+count-based mAP/CMC at Market sizes; gallery-sharded across ranks with an
+all-gather of queries; reported as distmat_GBps etc.), the end-to-end JPEG
+stage, the Duke and sharded legs, the CPU baseline and the GPU clock samples.
+The --no-* / --sharded-legs / --dist-reps / --e2e-images switches select
+among those and mean nothing without --full.
 
 Multi-GPU: launched by torch.distributed.run, one process per GPU, RCCL.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -49,9 +59,16 @@ def parse():
     p.add_argument('--gpus', type=int, default=None,
                    help='ranks (one per GPU); > 1 without WORLD_SIZE in the environment '
                         'launches them (torch.distributed.run, before any GPU call)')
-    p.add_argument('--steps', type=int, default=20)
+    p.add_argument('--steps', type=int, default=20, help='timed steps (>= 1)')
     p.add_argument('--warmup', type=int, default=3)
     p.add_argument('--batch', type=int, default=64)
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run every other measurement (PCIe-inclusive '
+                        'rate, rooflines, retrieval, e2e, Duke / sharded legs, CPU baseline, GPU '
+                        'clock samples); the --no-* switches below select among them')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='write what the last timed step computed to DIR/features.npy (float32 '
+                        '[batch, feat_dim]; DIR/features_rank<r>.npy per rank at N > 1)')
     p.add_argument('--no-graph', action='store_true', help='eager launches (no hipGraph)')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--no-duke', action='store_true',
@@ -69,8 +86,12 @@ def parse():
     p.add_argument('--no-sharded-legs', action='store_true')
     p.add_argument('--tiles-file', default=None,
                    help='JSON {layer: tile}: reuse (if present) or save the autotune result, '
-                        'so profiling passes run the same kernels as the timed run')
-    return p.parse_args()
+                        'so profiling passes run the same kernels as the timed run (saved by '
+                        '--full runs, which also tune the distance tile)')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    return args
 
 
 def launch_ranks(n):
@@ -1048,7 +1069,7 @@ def main():
     backend = os.environ.get('PPS_DIST_BACKEND', 'nccl')
     if backend == 'gloo':
         local = local % torch.cuda.device_count()
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         # JPEG decode processes for the e2e stage, forked from a server started
         # before this process touches the GPU; the host's CPUs split over the
         # node's ranks
@@ -1085,7 +1106,6 @@ def main():
     cfg = market_cfg()
     H, W = cfg.REID.SCALE[1], cfg.REID.SCALE[0]
     feat = torch.empty((B, nm.feat_dim), dtype=torch.float32, device='cuda')
-    from pps_amd import ops
     nm.reserve(B)
 
     def step():   # uint8 images -> preprocess -> forward, one C call
@@ -1106,7 +1126,8 @@ def main():
 
     pdist.barrier(world)
     torch.cuda.synchronize()
-    with ClockSampler(local) as clk:
+    # (--full: the shader clock sampled from a host thread meanwhile)
+    with (ClockSampler(local) if args.full else contextlib.nullcontext()) as clk:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             run()
@@ -1116,11 +1137,61 @@ def main():
     elapsed = pdist.max_over_ranks(elapsed, world)
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * B * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, feat, rank, world)
+    out = {
+        'metric': 'gallery images/sec + distmat GB/s; mAP/Rank-1 parity on Market-1501',
+        'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        # f32 operands and outputs; the products run as exact-split f16 / bf16
+        # MFMA terms with f32 accumulation (DESIGN §3)
+        'dtype': ('f32 (f16x2 3-term / bf16x3 6-term MFMA emulation, f32 accumulate)'
+                  if nm.math == 'x3' else 'f32 (f32 MFMA)'),
+        'data': 'synthetic (uint8 images, seeded weights of the PPS R-50 architecture)',
+        'config': {'workload': 'Market-1501 ResNet-50 PPS (stride-1 res5, 31 part subsets), '
+                               'batch %d/GPU, 384x128, 3368q x 15913g L2 distmat' % B,
+                   'global_batch': B * world, 'input_hw': [H, W], 'feat_dim': nm.feat_dim,
+                   'parallelism': 'dp%d' % world, 'hipgraph': not args.no_graph,
+                   'entry_point': 'pps_forward_bgr (whole-network C ABI)',
+                   'act_plane_edges': len(nm.planes()), 'splitk_layers': len(nm.splitks()),
+                   'tuning_table': table_digest(nm)},
+        'full': bool(args.full),
+    }
+    if args.full:
+        pcie = pcie_inclusive(args, world, imgs, run)
+        del graph, run
+        out.update(full_stages(args, rank, world, nm, blobs, xbuf, clk, pcie))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
-    # PCIe-inclusive rate: the test loop hands the library host
-    # images, so also time the step with each batch's uint8 images copied
-    # from pinned host memory first (same stream, ordered before the replay).
-    # Reported beside `value`, never as it.
+
+def dump_outputs(path, feat, rank, world):
+    """--dump-outputs: the feature batch the last timed step left in its
+    output buffer (what a caller of pps_forward_bgr receives), float32
+    [batch, feat_dim], as <path>/features.npy (features_rank<r>.npy per rank
+    at N > 1).  Weights and images are seeded, so two builds run with the same
+    arguments are comparable feature for feature.  A batch above 64 MB is
+    written as a seeded sample of its rows (ascending)."""
+    os.makedirs(path, exist_ok=True)
+    name = 'features.npy' if world == 1 else 'features_rank%d.npy' % rank
+    cap = (64 * 10 ** 6 // max(world, 1)) // (feat.shape[1] * 4)
+    if feat.shape[0] > cap:
+        rows = np.sort(np.random.RandomState(0).choice(feat.shape[0], cap, replace=False))
+        feat = feat[torch.from_numpy(rows).to(feat.device)]
+    np.save(os.path.join(path, name), feat.detach().cpu().numpy().astype(np.float32, copy=False))
+
+
+def pcie_inclusive(args, world, imgs, run):
+    """PCIe-inclusive rate: the test loop hands the library host
+    images, so also time the step with each batch's uint8 images copied
+    from pinned host memory first (same stream, ordered before the replay).
+    Reported beside `value`, never as it."""
+    from pps_amd import distributed as pdist
+    B = args.batch
     host = torch.empty(imgs.shape, dtype=torch.uint8, pin_memory=True)
     host.copy_(imgs.cpu())
     for _ in range(2):
@@ -1135,12 +1206,20 @@ def main():
     torch.cuda.synchronize()
     pdist.barrier(world)
     el_h2d = pdist.max_over_ranks(time.perf_counter() - t0, world)
-    pcie = dict(value=round(world * B * args.steps / el_h2d, 2), unit='images/s',
+    return dict(value=round(world * B * args.steps / el_h2d, 2), unit='images/s',
                 ms_per_step=round(el_h2d * 1e3 / args.steps, 3),
                 h2d_bytes_per_step=int(host.numel()),
                 note='uint8 BGR batch copied from pinned host memory before every step')
-    del graph
 
+
+def full_stages(args, rank, world, nm, blobs, xbuf, clk, pcie):
+    """--full: everything the line reports beside `value`, run after the
+    timed steps (and after pcie_inclusive, which replays the same graph):
+    conv roofline, retrieval stage with its rooflines, the e2e JPEG stage, the
+    sharded / Duke legs and the CPU baseline.  Returns the extra keys."""
+    from pps_amd import ops
+    from pps_amd import distributed as pdist
+    B = args.batch
     roof, per_layer = conv_roofline(nm, xbuf)
     tiles_saved = bool(args.tiles_file and os.path.exists(args.tiles_file))
     ret = retrieval_stage(rank, world, args.dist_reps,
@@ -1164,14 +1243,6 @@ def main():
     dist_ms_max = pdist.max_over_ranks(ret['distmat_ms'], world)
     total_bytes = (Q_MARKET + G_MARKET) * D_FEAT * 4 + Q_MARKET * G_MARKET * 4
     out = {
-        'metric': 'gallery images/sec + distmat GB/s; mAP/Rank-1 parity on Market-1501',
-        'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world,
-        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3),
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        # f32 operands and outputs; the products run as exact-split f16 / bf16
-        # MFMA terms with f32 accumulation (DESIGN §3)
-        'dtype': ('f32 (f16x2 3-term / bf16x3 6-term MFMA emulation, f32 accumulate)'
-                  if nm.math == 'x3' else 'f32 (f32 MFMA)'),
         'math': dict(conv_launches=dict(
                          f16x2=sum(1 for v in per_layer.values()
                                    if v['gemm'] and v['tile'] & ops.TILE_H2),
@@ -1180,14 +1251,6 @@ def main():
                      distance=ops.dist_math(), accumulate='f32',
                      note='f16x2: each f32 operand as two f16 terms on a power-of-two scale, '
                           'three f16 MFMA products; bf16x3: three bf16 terms, six products'),
-        'data': 'synthetic (uint8 images, seeded weights of the PPS R-50 architecture)',
-        'config': {'workload': 'Market-1501 ResNet-50 PPS (stride-1 res5, 31 part subsets), '
-                               'batch %d/GPU, 384x128, 3368q x 15913g L2 distmat' % B,
-                   'global_batch': B * world, 'input_hw': [H, W], 'feat_dim': nm.feat_dim,
-                   'parallelism': 'dp%d' % world, 'hipgraph': not args.no_graph,
-                   'entry_point': 'pps_forward_bgr (whole-network C ABI)',
-                   'act_plane_edges': len(nm.planes()), 'splitk_layers': len(nm.splitks()),
-                   'tuning_table': table_digest(nm)},
         'gpu_clock': clk.summary(),
         'distmat_GBps': round(total_bytes / (dist_ms_max * 1e-3) / 1e9, 2),
         'distmat_ms': round(dist_ms_max, 3),
@@ -1245,14 +1308,10 @@ def main():
         torch.cuda.empty_cache()
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(blobs)
-    if rank == 0:
-        if os.environ.get('PPS_BENCH_LAYERS'):
-            with open(os.environ['PPS_BENCH_LAYERS'], 'w') as f:
-                json.dump({k: v for k, v in per_layer.items()}, f, indent=0)
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    if rank == 0 and os.environ.get('PPS_BENCH_LAYERS'):
+        with open(os.environ['PPS_BENCH_LAYERS'], 'w') as f:
+            json.dump({k: v for k, v in per_layer.items()}, f, indent=0)
+    return out
 
 
 if __name__ == '__main__':

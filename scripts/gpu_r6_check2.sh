@@ -12,7 +12,7 @@ grep -E "passed|failed|FAILED|ERROR" $OUT/r6_check2.log | tail -5
 [ $rc -eq 0 ] || exit $rc
 [ -n "$NO_BENCH" ] && exit 0
 for r in 1 2; do
-  timeout -k 10 600 python -u bench.py --no-e2e --no-cpu-baseline --tiles-file $OUT/tiles_c2_$r.json \
+  timeout -k 10 600 python -u bench.py --full --no-e2e --no-cpu-baseline --tiles-file $OUT/tiles_c2_$r.json \
       > $OUT/r6_bench_c2_$r.log 2>&1 || { tail -20 $OUT/r6_bench_c2_$r.log; exit 1; }
   tail -1 $OUT/r6_bench_c2_$r.log | cut -c1-330
   python -c "import json; t=json.load(open('$OUT/tiles_c2_$r.json')); print('stem', t.get('conv1'))"

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
-timeout -k 10 900 python -u bench.py --sharded-legs --no-e2e --no-duke --no-cpu-baseline \
+timeout -k 10 900 python -u bench.py --full --sharded-legs --no-e2e --no-duke --no-cpu-baseline \
     > $OUT/r6_legs.log 2>&1 || { tail -20 $OUT/r6_legs.log; exit 1; }
 tail -1 $OUT/r6_legs.log | python -c "
 import json, sys

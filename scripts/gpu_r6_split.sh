@@ -18,6 +18,6 @@ done
 timeout -k 10 120 python -u scripts/probes/dual_once.py 45 --shape res5 >> $L 2>&1 || { tail -5 $L; exit 1; }
 grep -E "tile" $L
 for r in 1 2; do
-  timeout -k 10 600 python -u bench.py --no-e2e --no-cpu-baseline --no-duke > $OUT/r6_bench_split_$r.log 2>&1 || { tail -20 $OUT/r6_bench_split_$r.log; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --no-e2e --no-cpu-baseline --no-duke > $OUT/r6_bench_split_$r.log 2>&1 || { tail -20 $OUT/r6_bench_split_$r.log; exit 1; }
   tail -1 $OUT/r6_bench_split_$r.log | cut -c1-200
 done

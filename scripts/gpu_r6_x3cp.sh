@@ -19,7 +19,7 @@ for shape in res2b res3b res4b res5b; do
 done
 grep -E "tile" $L
 for r in 1 2; do
-  timeout -k 10 600 python -u bench.py --no-e2e --no-cpu-baseline --no-duke --tiles-file $OUT/tiles_x3cp_$r.json > $OUT/r6_bench_x3cp_$r.log 2>&1 || { tail -20 $OUT/r6_bench_x3cp_$r.log; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --no-e2e --no-cpu-baseline --no-duke --tiles-file $OUT/tiles_x3cp_$r.json > $OUT/r6_bench_x3cp_$r.log 2>&1 || { tail -20 $OUT/r6_bench_x3cp_$r.log; exit 1; }
   tail -1 $OUT/r6_bench_x3cp_$r.log | cut -c1-160
   python -c "
 import json; t = json.load(open('$OUT/tiles_x3cp_$r.json'))

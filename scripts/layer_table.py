@@ -3,7 +3,7 @@ GFLOP, algorithmic MB, us, TF, fraction of the x3 roof, MFMA busy (over the
 launch's trace duration at 2.4 GHz: a lower bound; no GRBM-derived clock, see
 pmc_traffic.py), memory-side FETCH/WRITE MB per launch.
 
-  python scripts/layer_table.py <layers.json (bench.py PPS_BENCH_LAYERS)> <pmcb dir> > table.md
+  python scripts/layer_table.py <layers.json (bench.py --full, PPS_BENCH_LAYERS)> <pmcb dir> > table.md
 
 layers.json holds the bench's per-launch HIP-event times in forward order;
 pmcb/p1..p3 are the PMC passes of scripts/gpu_profile.sh (FETCH_SIZE;

@@ -1,8 +1,8 @@
 """HBM traffic per launch of the bench's dominant kernels from two rocprofv3
 PMC passes (FETCH_SIZE, WRITE_SIZE; separate passes, --kernel-trace only):
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir>/p1 -o run --output-format csv -- python3 bench.py ...
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir>/p2 -o run --output-format csv -- python3 bench.py ...
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir>/p1 -o run --output-format csv -- python3 bench.py --full ...
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir>/p2 -o run --output-format csv -- python3 bench.py --full ...
   python scripts/pmc_traffic.py <dir> <math> <batch> <launches per forward> [tiles.json]
       [--clock-from <bench log>] > profiles/rNN/pmc_traffic.json
 

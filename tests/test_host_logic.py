@@ -70,6 +70,41 @@ def test_bench_gpus_must_match_world_size():
     assert rc != 0 and not lines and '--gpus 4 but WORLD_SIZE=2' in err
 
 
+def test_bench_full_and_dump_outputs_are_options():
+    """--full and --dump-outputs parse beside the plain arguments (--dry-run:
+    no GPU work), and --steps must name at least one timed step."""
+    rc, lines, err = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--full',
+                             '--dump-outputs', os.devnull, '--dry-run'])
+    assert rc == 0, err[-2000:]
+    assert len(lines) == 1 and lines[0]['steps'] == 3 and lines[0]['ms_per_step'] >= 0
+    rc, lines, err = _bench(['--steps', '0', '--dry-run'])
+    assert rc != 0 and not lines and '--steps' in err
+
+
+def test_bench_dump_outputs_file(tmp_path):
+    """dump_outputs writes the feature batch as float32 <dir>/features.npy
+    (per-rank names at N > 1), the same bytes on every call, and a batch over
+    the 64 MB cap as a fixed ascending sample of its rows."""
+    import torch
+    import bench
+    feat = torch.arange(6 * 8, dtype=torch.float32).reshape(6, 8) / 7
+    d = str(tmp_path / 'out')
+    bench.dump_outputs(d, feat, 0, 1)
+    got = np.load(os.path.join(d, 'features.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, feat.numpy())
+    bench.dump_outputs(d, feat, 1, 2)
+    assert np.array_equal(np.load(os.path.join(d, 'features_rank1.npy')), feat.numpy())
+    wide = torch.zeros((5, 4 * 10 ** 6), dtype=torch.float32)   # 16 MB a row: 4 rows fit
+    wide[:, 0] = torch.arange(5)
+    picks = []
+    for _ in range(2):
+        bench.dump_outputs(d, wide, 0, 1)
+        got = np.load(os.path.join(d, 'features.npy'))
+        assert got.shape == (4, 4 * 10 ** 6) and got.nbytes <= 64 * 10 ** 6
+        picks.append(got[:, 0].tolist())
+    assert picks[0] == picks[1] == sorted(picks[0])
+
+
 def test_decode_pool_matches_in_process_decode(tmp_path):
     """The decode processes return exactly what decode_bgr returns in the
     calling process (BGR uint8, source shapes kept), in order."""
