@@ -487,6 +487,27 @@ int pps_topk_merge(const float* vals, const int32_t* idx, int R, int64_t Q, int 
                    const int64_t* list_offsets, int k_out, float* out_vals,
                    int32_t* out_idx, void* stream);
 
+/* Fused f16x2 distance + stable top-k: vals / idx [Q][k] = the k nearest
+ * gallery rows of every query, ascending, ties by gallery index -- bit for
+ * bit pps_topk over the matrix pps_distmat_h2_tiled would write, which is
+ * never materialised.  Operands and their checks are pps_distmat_h2_tiled's.
+ * 1 <= k <= pps_search_max_k(); rows past G entries are padded with
+ * (+inf, -1).  segments: gallery segments searched by independent workgroups
+ * and merged (0 = auto; clamped to the gallery's tile count, 64 and 8192 / k);
+ * tile: 0 = default, 1..pps_search_h2_num_tiles()-1 (same bits, speed only).
+ * workspace: a 256-byte aligned device buffer of at least
+ * pps_search_h2_workspace_bytes(Q, G, k, segments) bytes (host function,
+ * non-decreasing in G; -1 on bad arguments); a smaller one fails with
+ * PPS_ERR_CAPACITY before anything is launched. */
+int pps_search_max_k(void);
+int pps_search_h2_num_tiles(void);
+int64_t pps_search_h2_workspace_bytes(int64_t Q, int64_t G, int k, int segments);
+int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                        const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                        int D, int metric, int k, int segments, int tile,
+                        void* workspace, int64_t ws_bytes,
+                        float* vals, int32_t* idx, void* stream);
+
 /* k-reciprocal re-ranking (reid_dataset_evaluator.py:442-519): out [Q][G] =
  * re_ranking(q_g, q_q, g_g, k1, k2, lambda) with the reference's float32
  * operand order for V, V_qe and the Jaccard sums; ties in the initial rank use

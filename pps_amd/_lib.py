@@ -96,6 +96,8 @@ SIGNATURES = {
                        c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'pps_cmc_finalize': [c_i64, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'pps_topk_merge': [c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    'pps_search_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
+                            c_int, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],
@@ -185,6 +187,9 @@ EXTRA = {
     'pps_abi_version': ([], ctypes.c_int),
     'pps_gemm_num_tiles': ([], ctypes.c_int),
     'pps_h2_num_tiles': ([], ctypes.c_int),
+    'pps_search_max_k': ([], ctypes.c_int),
+    'pps_search_h2_num_tiles': ([], ctypes.c_int),
+    'pps_search_h2_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
     'pps_rank_cells': ([], ctypes.c_int),
     'pps_argsort_rows_cap': ([], ctypes.c_int),
     'pps_stem_k': ([], ctypes.c_int),

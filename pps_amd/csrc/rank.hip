@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "gemm_common.hpp"
+#include "topk_wave_common.hpp"
 
 namespace pps {
 
@@ -952,16 +953,8 @@ int cmc_finalize(int64_t Q, int Ptot, const int32_t* pos_total, const int32_t* h
 // ---- stable per-row top-k ---------------------------------------------------------
 // Radix select (4 x 8-bit digits of the order-preserving key) finds the k-th
 // smallest key K*; entries with key < K*, then entries == K* in index order,
-// are compacted into LDS and bitonic-sorted as 64-bit (key << 32 | index).
-__device__ inline uint32_t float_key(float f) {
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float key_float(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
-
+// are compacted into LDS and bitonic-sorted as 64-bit (key << 32 | index)
+// (float_key / key_float: topk_wave_common.hpp).
 constexpr int kTopkThreads = 256;
 constexpr int kTopkCap = 1024;      // max k
 constexpr int kTopkBuf = 4096;      // candidate buffer (64-bit entries) in LDS
@@ -1223,88 +1216,12 @@ constexpr int kTkwU = PPS_TKW_U;            // float4 per lane per iteration
 constexpr int kTkwIter = 64 * 4 * kTkwU;    // row entries per wave iteration (512)
 constexpr int kTkwWaves = kTopkThreads / 64;
 constexpr int kTkwMinRow = 16384;           // rows at least this long take this kernel
-constexpr int kTkwMaxK = 256;
-constexpr int kTkwSlack = 64;               // a streaming cut keeps k .. k + slack entries
 // per-wave buffer: what a cut keeps + one iteration's worst-case inflow
 __host__ __device__ constexpr int tkw_cap(int k) { return (k + kTkwSlack + kTkwIter + 63) / 64 * 64; }
 // registers per lane for a wave's buffer / the four merged lists, for k <= KM
 template <int KM> constexpr int tkw_j() { return tkw_cap(KM) / 64; }
 template <int KM> constexpr int tkw_merge_j() { return kTkwWaves * KM / 64 + 1; }
-
-__device__ inline void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-__device__ inline unsigned long long wave_min_u64(unsigned long long x) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_xor(x, o);
-    x = y < x ? y : x;
-  }
-  return x;
-}
-__device__ inline unsigned long long wave_max_u64(unsigned long long x) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_xor(x, o);
-    x = y > x ? y : x;
-  }
-  return x;
-}
-template <int J>
-__device__ inline int wave_count_le(const unsigned long long (&v)[J], unsigned long long t) {
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < J; ++j) c += __popcll(__ballot(v[j] <= t));
-  return c;
-}
-
-// v[j] holds entry j*64 + lane of a wave's n > k unique packed values (~0ull
-// past n; no real entry is ~0ull: indices are < 2^31).  Returns a T with
-// k <= count(v <= T) <= k + slack; slack 0 gives the k-th smallest value.
-// Invariant count(<= lo) < k <= count(<= hi); every value is wave-uniform.
-template <int J>
-__device__ unsigned long long wave_select(const unsigned long long (&v)[J], int k, int slack) {
-  unsigned long long mn = ~0ull, mx = 0ull;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    mn = v[j] < mn ? v[j] : mn;
-    mx = (v[j] != ~0ull && v[j] > mx) ? v[j] : mx;
-  }
-  mn = wave_min_u64(mn);
-  mx = wave_max_u64(mx);
-  if (k <= 1) return mn;
-  unsigned long long lo = mn, hi = mx;   // count(<= mn) = 1 < k
-  while (hi - lo > 1) {
-    const unsigned long long mid = lo + ((hi - lo) >> 1);
-    const int c = wave_count_le(v, mid);
-    if (c >= k && c <= k + slack) return mid;
-    if (c < k) lo = mid; else hi = mid;
-  }
-  return hi;
-}
-
-// Cuts a wave's buffer buf[0, n) to the entries <= T of wave_select: reads
-// it into registers, selects, writes the kept entries back to the front.
-// Returns T; n becomes the kept count.
-template <int J>
-__device__ unsigned long long wave_cut(unsigned long long* buf, int& n, int k, int slack) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long v[J];
-#pragma unroll
-  for (int j = 0; j < J; ++j) v[j] = j * 64 + lane < n ? buf[j * 64 + lane] : ~0ull;
-  const unsigned long long T = wave_select(v, k, slack);
-  int m = 0;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const bool keep = v[j] <= T;
-    const unsigned long long bal = __ballot(keep);
-    if (keep) buf[m + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = v[j];
-    m += __popcll(bal);
-  }
-  wave_lds_sync();
-  n = m;
-  return T;
-}
+// (wave_select / wave_cut: topk_wave_common.hpp)
 
 // RR (re-ranking, rerank.hip): row q is row q of OD for a symmetric M read
 // in place -- a virtual row of the M row's first block (Q entries, padded to

@@ -1,0 +1,369 @@
+// Fused f16x2 distance + stable top-k ("search"): the k nearest gallery rows
+// of every query without the [Q, G] distance matrix.
+//
+// Work item = (query panel of BM rows, gallery segment s of S).  A workgroup
+// walks the BN-column tiles of its segment; per tile it runs the K loop of
+// gemm_h2_kernel (h2_kloop: chunks ascending, mfma_h2t's three terms, f32
+// accumulation), parks the accumulators in LDS like h2_dist_epilogue and
+// finishes each distance with the same expression,
+//   dist_value(p, (acc * rs_a) * rs_b, qn, gn),
+// so every value has the bits pps_distmat_h2_tiled would have written.
+// Instead of storing them, each wave filters its rows of the parked tile:
+// a column survives if its packed (float_key(d) << 32 | column) value is not
+// above the row's threshold and is appended to the row's candidate buffer;
+// when the next pass could overflow the buffer the wave cuts it back to
+// between k and k + kTkwSlack entries (wave_cut, the select of
+// topk_wave_kernel) and the cut's bound becomes the threshold.  After the
+// segment's last tile the row's exact k best are sorted and written to the
+// partial list [S][Q][k] (ascending, ties by column, segment-local columns);
+// topk_merge joins the S lists on the same stream.  The stable (distance,
+// index) top-k is unique, so the result equals topk(distmat) bit for bit for
+// every tile and segment count.
+//
+// No workgroup waits on another: a work item touches only its own candidate
+// buffers (one set per launched workgroup, reused over the items the
+// workgroup strides through) and its own partial list.
+//
+// LDS: the pipeline stages / the parked tile as in gemm_h2_kernel, plus 16
+// bytes of row state (threshold, count) per query row beside them.  The
+// candidate buffers live in the caller's workspace.
+#include <algorithm>
+
+#include "gemm_h2_common.hpp"
+#include "topk_wave_common.hpp"
+
+namespace pps {
+
+constexpr int kSearchNumTiles = 3;   // 0 = default (1), 1 = 256 x 256 two-stage, 2 = 192 x 192 three-stage
+constexpr int kSearchSlots = 256;    // workgroups launched at most: one per CU (LDS-bound residency)
+constexpr int kSearchMaxBM = 256;    // rows of a slot's buffer set
+constexpr int kSearchInflow = 256;   // most columns a row can receive between two cut checks
+// entries of one row's candidate buffer: what a cut keeps + one pass's inflow
+constexpr int search_cap(int k) { return (k + kTkwSlack + kSearchInflow + 63) / 64 * 64; }
+constexpr int kSearchJ = search_cap(kTkwMaxK) / 64;   // registers per lane of a cut
+
+struct SearchArgs {
+  int k, cap;
+  int S, tps, tiles_n;            // segments, gallery tiles per segment, gallery tiles
+  int64_t items;                  // panels * S
+  unsigned long long* cand;       // [slots][BM][cap]
+  float* pvals;                   // [S][Q][k]
+  int32_t* pidx;
+};
+
+// orders a wave's accesses to its candidate buffer in global memory (lane a's
+// store, lane b's later load)
+__device__ inline void wave_global_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+
+// ascending bitonic sort of buf[0, n2) (LDS), n2 a power of two, by one wave
+__device__ inline void wave_bitonic(unsigned long long* buf, int n2) {
+  const int lane = threadIdx.x & 63;
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = lane; t < n2 / 2; t += 64) {
+        const int i = 2 * stride * (t / stride) + (t % stride), j = i + stride;
+        const bool up = (i & size) == 0;
+        const unsigned long long a = buf[i], b = buf[j];
+        if ((a > b) == up) { buf[i] = b; buf[j] = a; }
+      }
+      wave_lds_sync();
+    }
+}
+
+__device__ inline unsigned long long uniform_u64(unsigned long long x) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <int BM, int BN, int WM, int WN, int NS>
+__global__ void __launch_bounds__(64 * WM * WN)
+search_h2_kernel(GemmParams p, SearchArgs a) {
+  using T = H2Tile<BM, BN, WM, WN, NS>;
+  constexpr int NW = T::NW, TM = T::TM, TN = T::TN, HB = T::HB;
+  constexpr int WCOLS = BN / WN;
+  constexpr int BNH = BN / HB, LD = BNH + 4;
+  constexpr int RPW = BM / NW;             // rows a wave filters
+  constexpr int CS = (BNH + 63) / 64;      // columns per lane and pass
+  static_assert(BM % NW == 0 && BM <= kSearchMaxBM, "rows per wave / slot rows");
+  static_assert(BNH <= kSearchInflow, "a pass's inflow is what search_cap leaves room for");
+  static_assert(BNH % WCOLS == 0, "a wave's columns fall in one pass");
+  static_assert(NW * kTkwMaxK * 8 <= T::LDS_BYTES, "sort scratch of the waves");
+  constexpr int STATE = T::LDS_BYTES;      // row state beside the stages / the parked tile
+  static_assert(STATE % 16 == 0 && STATE + BM * 16 <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[STATE + BM * 16];
+  unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(lds + STATE);
+  int* s_n = reinterpret_cast<int*>(lds + STATE + BM * 8);
+  float* t = reinterpret_cast<float*>(lds);
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave / WN, wn = wave - wm * WN;
+  const int r16 = lane & 15, h = lane >> 4;
+  const int wc0 = wn * WCOLS;
+  const int k = a.k, cap = a.cap;
+  unsigned long long* cand = a.cand + (int64_t)blockIdx.x * BM * cap;
+  unsigned long long* sbuf = reinterpret_cast<unsigned long long*>(lds) + wave * kTkwMaxK;
+
+  for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
+    const int panel = (int)(item / a.S), s = (int)(item - (int64_t)panel * a.S);
+    const int m0 = panel * BM;
+    const int mrem = p.M - m0;
+    const int t0 = s * a.tps, t1 = min(t0 + a.tps, a.tiles_n);
+    const int cbase = t0 * BN;   // the segment's first gallery column
+    // the rows of this wave start empty (only this wave touches their state)
+    for (int r = lane; r < RPW; r += 64) {
+      s_thr[wave * RPW + r] = ~0ull;   // inclusive: entries <= thr stay candidates
+      s_n[wave * RPW + r] = 0;
+    }
+
+    for (int tn = t0; tn < t1; ++tn) {
+      const int n0 = tn * BN;
+      const int nrem = p.Ncol - n0;
+      f32x4 acc[TM][TN];
+      h2_kloop<BM, BN, WM, WN, NS>(p, lds, m0, n0, wave, lane, wm, wn, acc);
+
+#pragma unroll
+      for (int hb = 0; hb < HB; ++hb) {
+        const int c0h = hb * BNH;
+        __syncthreads();  // the stages / the previous pass are no longer read
+        if (wc0 >= c0h && wc0 < c0h + BNH) {
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            const int row = wm * (BM / WM) + i * 16 + r16;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+              const int col = wc0 - c0h + j * 16 + 4 * h;
+              *reinterpret_cast<f32x4*>(t + row * LD + col) = acc[i][j];
+            }
+          }
+        }
+        __syncthreads();
+        // this lane's columns of the pass: norms and scales once for all rows
+        bool ok[CS];
+        float gn[CS], rb[CS];
+#pragma unroll
+        for (int j = 0; j < CS; ++j) {
+          const int c = j * 64 + lane;
+          ok[j] = c < BNH && c0h + c < nrem;
+          gn[j] = ok[j] ? p.norm_b[n0 + c0h + c] : 0.f;
+          rb[j] = ok[j] ? p.rs_b[n0 + c0h + c] : 0.f;
+        }
+        for (int i = 0; i < RPW; ++i) {
+          const int row = wave * RPW + i;   // wave-uniform
+          if (row >= mrem) break;
+          const int gr = m0 + row;
+          const float qn = p.norm_a[gr];
+          const float ra = p.rs_a[gr];
+          unsigned long long thr = uniform_u64(s_thr[row]);
+          int n = __builtin_amdgcn_readfirstlane(s_n[row]);
+          unsigned long long* buf = cand + (int64_t)row * cap;
+          // room for this pass; and once, as soon as a real threshold exists
+          if (n + BNH > cap || (thr == ~0ull && n > k + kTkwSlack)) {
+            wave_global_sync();
+            thr = wave_cut<kSearchJ>(buf, n, k, kTkwSlack);
+            wave_global_sync();
+          }
+#pragma unroll
+          for (int j = 0; j < CS; ++j) {
+            const int c = j * 64 + lane;
+            // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
+            const float dot = ok[j] ? t[row * LD + c] : 0.f;
+            const float d = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
+            const unsigned long long packed =
+                ((unsigned long long)float_key(d) << 32) | (uint32_t)(n0 + c0h + c - cbase);
+            const bool take = ok[j] && packed <= thr;
+            const unsigned long long bal = __ballot(take);
+            if (take)
+              buf[n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = packed;
+            n += __popcll(bal);
+          }
+          if (lane == 0) {
+            s_thr[row] = thr;
+            s_n[row] = n;
+          }
+        }
+      }
+      __syncthreads();  // the parked tile is no longer read: the next K loop may stage
+    }
+
+    // the segment's list: each row's exact k best, sorted in this wave's LDS scratch
+    int n2 = 1;
+    while (n2 < k) n2 <<= 1;
+    for (int i = 0; i < RPW; ++i) {
+      const int row = wave * RPW + i;
+      if (row >= mrem) break;
+      int n = __builtin_amdgcn_readfirstlane(s_n[row]);
+      unsigned long long* buf = cand + (int64_t)row * cap;
+      wave_global_sync();
+      if (n > k) {
+        wave_cut<kSearchJ>(buf, n, k, 0);
+        wave_global_sync();
+      }
+      for (int e = lane; e < n2; e += 64) sbuf[e] = e < n ? buf[e] : ~0ull;
+      wave_lds_sync();
+      wave_bitonic(sbuf, n2);
+      const int64_t o = ((int64_t)s * p.M + (m0 + row)) * k;
+      for (int e = lane; e < k; e += 64) {
+        const unsigned long long v = sbuf[e];
+        a.pvals[o + e] = e < n ? key_float((uint32_t)(v >> 32)) : __builtin_huge_valf();
+        a.pidx[o + e] = e < n ? (int32_t)(v & 0xffffffffu) : -1;
+      }
+      wave_lds_sync();   // sbuf is rewritten for the next row
+    }
+    __syncthreads();  // the sort scratch is free before the next item stages
+  }
+}
+
+__global__ void search_fill_pad_kernel(float* vals, int32_t* idx, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    vals[i] = __builtin_huge_valf();
+    idx[i] = -1;
+  }
+}
+
+// ---- host plan ---------------------------------------------------------------
+static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+
+static void search_tile_shape(int tile, int& BM, int& BN) {
+  if (tile == 2) { BM = 192; BN = 192; } else { BM = 256; BN = 256; }
+}
+
+// Segment count before it is rounded to whole tiles per segment: the request
+// (0 = auto: panels x S fills the CUs once or twice, whichever leaves the
+// smaller idle tail) under the clamps -- the segment's tile count, and
+// topk_merge's 64 lists and 8192 merged entries.  Non-decreasing in G.
+static int search_segments(int64_t Q, int64_t G, int k, int segments, int BM, int BN) {
+  const int64_t panels = std::max<int64_t>(cdiv(Q, BM), 1), tiles_n = std::max<int64_t>(cdiv(G, BN), 1);
+  int64_t S = segments;
+  if (S <= 0) {
+    const int64_t s1 = std::max<int64_t>(kSearchSlots / panels, 1);
+    const int64_t s2 = std::max<int64_t>(2 * kSearchSlots / panels, 1);
+    auto fill = [&](int64_t s) {
+      const int64_t items = panels * s;
+      return (double)items / (double)(cdiv(items, kSearchSlots) * kSearchSlots);
+    };
+    S = fill(s2) > fill(s1) ? s2 : s1;
+  }
+  S = std::min<int64_t>(S, tiles_n);
+  S = std::min<int64_t>(S, kMergeMaxLists);
+  S = std::min<int64_t>(S, 8192 / k);
+  return (int)std::max<int64_t>(S, 1);
+}
+
+struct SearchLayout {
+  int64_t cand_bytes, part_entries, total;
+};
+// tile-independent (the larger need of the two tile shapes)
+static SearchLayout search_layout(int64_t Q, int64_t G, int k, int segments) {
+  int S = 1;
+  int64_t slots = 1;   // workgroups launched: one buffer set each
+  for (int tile = 1; tile < kSearchNumTiles; ++tile) {
+    int BM, BN;
+    search_tile_shape(tile, BM, BN);
+    const int St = search_segments(Q, G, k, segments, BM, BN);
+    S = std::max(S, St);
+    slots = std::max(slots, std::min<int64_t>(kSearchSlots, cdiv(Q, BM) * St));
+  }
+  SearchLayout L;
+  L.cand_bytes = align256(slots * kSearchMaxBM * search_cap(k) * 8);
+  L.part_entries = (int64_t)S * Q * k;
+  L.total = L.cand_bytes + 2 * align256(L.part_entries * 4);
+  return L;
+}
+
+template <int BM, int BN, int WM, int WN, int NS>
+static int launch_search(const GemmParams& p, SearchArgs a, hipStream_t st) {
+  const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
+  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS>), dim3((unsigned)grid),
+                     dim3(64 * WM * WN), 0, st, p, a);
+  PPS_CHECK_LAUNCH("search_h2_kernel");
+  return PPS_OK;
+}
+
+}  // namespace pps
+
+// ---- C ABI ----------------------------------------------------------------
+using namespace pps;
+
+int pps_search_max_k(void) { return kTkwMaxK; }
+
+int pps_search_h2_num_tiles(void) { return kSearchNumTiles; }
+
+int64_t pps_search_h2_workspace_bytes(int64_t Q, int64_t G, int k, int segments) {
+  if (Q < 0 || G < 0 || k < 1 || k > kTkwMaxK || segments < 0) return -1;
+  return search_layout(Q, G, k, segments).total;
+}
+
+int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                        const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                        int D, int metric, int k, int segments, int tile, void* workspace,
+                        int64_t ws_bytes, float* vals, int32_t* idx, void* stream) {
+  PPS_ENFORCE(vals && idx, "null pointer");
+  PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
+  PPS_ENFORCE(Q < (1ll << 31), "Q must fit int32");
+  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
+  PPS_ENFORCE(k >= 1 && k <= kTkwMaxK, "k must be in [1, " + std::to_string(kTkwMaxK) + "]");
+  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
+  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
+              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
+  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
+  PPS_ENFORCE(2 * Qp * D * 2 < kMaxBufBytes && 2 * Gp * D * 2 < kMaxBufBytes,
+              "planes over 2 GiB");
+  if (Q == 0) return PPS_OK;
+  hipStream_t st = as_stream(stream);
+  if (G == 0) {  // nothing to rank: pad entries only
+    const int64_t n = Q * k;
+    hipLaunchKernelGGL(search_fill_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       vals, idx, n);
+    PPS_CHECK_LAUNCH("search_fill_pad_kernel");
+    return PPS_OK;
+  }
+  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
+  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  const SearchLayout L = search_layout(Q, G, k, segments);
+  if (!workspace || ws_bytes < L.total) {
+    set_error("pps_search_h2_tiled: workspace of " + std::to_string(ws_bytes) + " bytes, need " +
+              std::to_string(L.total));
+    return PPS_ERR_CAPACITY;
+  }
+  PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+
+  int BM, BN;
+  search_tile_shape(tile, BM, BN);
+  const int64_t panels = (Q + BM - 1) / BM, tiles_n = (G + BN - 1) / BN;
+  const int S0 = search_segments(Q, G, k, segments, BM, BN);
+  SearchArgs a{};
+  a.k = k;
+  a.cap = search_cap(k);
+  a.tiles_n = (int)tiles_n;
+  a.tps = (int)((tiles_n + S0 - 1) / S0);
+  a.S = (int)((tiles_n + a.tps - 1) / a.tps);   // no empty segment
+  a.items = panels * a.S;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  a.cand = reinterpret_cast<unsigned long long*>(ws);
+  a.pvals = reinterpret_cast<float*>(ws + L.cand_bytes);
+  a.pidx = reinterpret_cast<int32_t*>(ws + L.cand_bytes + (L.total - L.cand_bytes) / 2);
+
+  GemmParams p{};
+  p.splitk = 1;
+  p.tiled = 3;
+  p.a3 = q2t; p.a_plane = Qp * D; p.a_bytes = (uint32_t)(2 * Qp * D * 2);
+  p.M = (int)Q;
+  p.b3 = g2t; p.b_plane = Gp * D; p.b_bytes = (uint32_t)(2 * Gp * D * 2);
+  p.Ncol = (int)G;
+  p.Kloop = D;
+  p.norm_a = qsq; p.norm_b = gsq;
+  p.rs_a = qrs; p.rs_b = grs;
+  p.metric = metric;
+
+  const int rc = tile == 2 ? launch_search<192, 192, 2, 4, 3>(p, a, st)
+                           : launch_search<256, 256, 2, 4, 2>(p, a, st);
+  if (rc != PPS_OK) return rc;
+  MergeOffsets offs{};
+  for (int s = 0; s < a.S; ++s) offs.off[s] = (int64_t)s * a.tps * BN;
+  return topk_merge(a.pvals, a.pidx, a.S, Q, k, offs, k, vals, idx, st);
+}

@@ -185,6 +185,11 @@ class HipBackend(object):
         return ops.topk_merge(vals, idx, offsets, k)
 
     @staticmethod
+    def search(q, g, metric, k):
+        """Local rank list without the [Q, G] matrix (ops.search)."""
+        return ops.search(q, g, k, metric=metric)
+
+    @staticmethod
     def group_mean(x, groups):
         return ops.group_mean(x, groups)
 
@@ -295,29 +300,37 @@ class ShardedEvaluator(object):
             res['t_total_ms'] = evs[0].elapsed_time(evs[3])
         return res
 
-    def rank_list(self, q_local=None, g_local=None, k=100, dist=None):
+    def rank_list(self, q_local=None, g_local=None, k=100, dist=None, fused=False):
         """Global stable top-k rank list [Q, k] (distances, global gallery
-        indices) on every rank: local top-k, all-gather, k-way merge."""
+        indices) on every rank: local top-k, all-gather, k-way merge.
+        fused=True (no `dist` given, a backend with `search`): the local list
+        comes from the fused distance + top-k search, which never writes this
+        shard's [Q, G] matrix; same result with a small fixed workspace.  Off by
+        default: measured, the materialised path is the faster one (1.25x at the
+        Market shape, 1.04x at a 125k-row shard; DESIGN.md "Fused search")."""
         be = self.backend
-        if dist is None:
+        vals = idx = None
+        if fused and dist is None and hasattr(be, 'search'):
             q_all = all_gather_rows(q_local, self.q_sizes)
-            dist = be.distmat(q_all, g_local, self.metric)
-        kin = min(k, dist.shape[1])
-        if kin > 0:
-            vals, idx = be.topk(dist, kin)
+            dev = q_all.device
+            kin = min(k, g_local.shape[0])
+            if kin > 0:
+                vals, idx = be.search(q_all, g_local, self.metric, kin)
         else:
-            vals = torch.zeros((self.Q, 1), dtype=torch.float32, device=dist.device)
-            idx = torch.full((self.Q, 1), -1, dtype=torch.int32, device=dist.device)
-        if kin < k and kin > 0:   # short shard: pad its list to k entries
-            pv = torch.full((self.Q, k), float('inf'), dtype=torch.float32, device=dist.device)
-            pi = torch.full((self.Q, k), -1, dtype=torch.int32, device=dist.device)
-            pv[:, :kin] = vals
-            pi[:, :kin] = idx
+            if dist is None:
+                q_all = all_gather_rows(q_local, self.q_sizes)
+                dist = be.distmat(q_all, g_local, self.metric)
+            dev = dist.device
+            kin = min(k, dist.shape[1])
+            if kin > 0:
+                vals, idx = be.topk(dist, kin)
+        if kin < k:   # short (or empty) shard: pad its list to k entries
+            pv = torch.full((self.Q, k), float('inf'), dtype=torch.float32, device=dev)
+            pi = torch.full((self.Q, k), -1, dtype=torch.int32, device=dev)
+            if kin > 0:
+                pv[:, :kin] = vals
+                pi[:, :kin] = idx
             vals, idx = pv, pi
-        elif kin == 0:
-            vals = torch.full((self.Q, k), float('inf'), dtype=torch.float32,
-                              device=dist.device)
-            idx = torch.full((self.Q, k), -1, dtype=torch.int32, device=dist.device)
         vals, idx = self._gather_lists(vals.contiguous(), idx.contiguous())
         offsets = [a for a, _ in self.g_ranges]
         return be.topk_merge(vals.contiguous(), idx.contiguous(), offsets, k)

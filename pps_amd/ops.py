@@ -184,6 +184,29 @@ class GalleryIndex(object):
             self._planes = split_bf16x3(g)
             self.sqnorm = row_sqnorm(g)
 
+    @staticmethod
+    def split_rows(G, D, max_rows=None):
+        """Row ranges [(start, rows), ...] of a G-row gallery cut into
+        consecutive segments of at most max_rows rows; every segment but the
+        last is a multiple of 16 rows.  max_rows None = the largest multiple of
+        16 whose two f16 planes stay under the 2 GiB one index can address
+        (2 * rows * D * 2 bytes < 2^31)."""
+        G, D = int(G), int(D)
+        limit = ((2 ** 31 - 1) // (4 * D)) // 16 * 16
+        if limit < 16:
+            raise RuntimeError('GalleryIndex.split: D=%d too wide for one 16-row block' % D)
+        step = limit if max_rows is None else min(limit, max(16, int(max_rows) // 16 * 16))
+        return [(a, min(step, G - a)) for a in range(0, G, step)] or [(0, 0)]
+
+    @classmethod
+    def split(cls, g, max_rows=None, math=None):
+        """A gallery larger than one index may be: a list of GalleryIndex over
+        consecutive row segments (split_rows), which ops.search takes as one
+        logical gallery and answers with global indices."""
+        if g.dim() != 2:
+            raise RuntimeError('gallery must be [G, D], got %s' % (tuple(g.shape),))
+        return [cls(g[a:a + n], math=math) for a, n in cls.split_rows(g.shape[0], g.shape[1], max_rows)]
+
     @property
     def shape(self):
         return self.feats.shape
@@ -449,6 +472,145 @@ def topk_merge(vals, idx, offsets, k):
          offs.ctypes.data_as(_lib.ctypes.c_void_p), k, out_v.data_ptr(), out_i.data_ptr(),
          _stream())
     return out_v, out_i
+
+
+def search_max_k():
+    """Largest k of the fused search kernel (pps_search_max_k)."""
+    return int(_lib.lib().pps_search_max_k())
+
+
+def search_num_tiles():
+    return int(_lib.lib().pps_search_h2_num_tiles())
+
+
+def search_workspace_bytes(Q, G, k, segments=0):
+    """Bytes of device workspace one fused search of Q queries against a G-row
+    index needs (pps_search_h2_workspace_bytes; host arithmetic only,
+    non-decreasing in G)."""
+    n = int(_lib.lib().pps_search_h2_workspace_bytes(int(Q), int(G), int(k), int(segments)))
+    if n < 0:
+        raise RuntimeError('search_workspace_bytes: bad arguments Q=%r G=%r k=%r segments=%r '
+                           '(1 <= k <= %d)' % (Q, G, k, segments, search_max_k()))
+    return n
+
+
+def _pad_list(vals, idx, k):
+    """[Q, kin] lists -> [Q, k], the tail (+inf, -1) (pps_topk_merge's pad)."""
+    Q, kin = vals.shape
+    if kin == k:
+        return vals, idx
+    pv = torch.full((Q, k), float('inf'), dtype=torch.float32, device=vals.device)
+    pi = torch.full((Q, k), -1, dtype=torch.int32, device=vals.device)
+    pv[:, :kin] = vals
+    pi[:, :kin] = idx
+    return pv, pi
+
+
+def _search_one(q, q_split, index, k, metric, segments, tile, workspace):
+    """One index: the fused kernel when it applies, else the matrix."""
+    Q, D = q.shape
+    G = index.shape[0]
+    fused = (index.h2 is not None and q_split is not None and 1 <= k <= search_max_k())
+    if not fused:
+        kin = min(k, G)
+        if kin == 0 or Q == 0:
+            return _pad_list(torch.empty((Q, 0), dtype=torch.float32, device=q.device),
+                             torch.empty((Q, 0), dtype=torch.int32, device=q.device), k)
+        qc = q if q.is_contiguous() else q.contiguous()   # compute_dist takes whole rows
+        vals, idx = topk(compute_dist(qc, index, metric=metric, pad_rows=True), kin)
+        return _pad_list(vals, idx, k)
+    q2, qrs, qsq = q_split
+    g2, grs, gsq = index.h2
+    need = search_workspace_bytes(Q, G, k, segments)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=q.device)
+    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
+          not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError('search: workspace must be a contiguous device tensor of at least '
+                           '%d bytes (search_workspace_bytes)' % need)
+    vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+    call('pps_search_h2_tiled', _dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
+         _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
+         D, METRICS[metric], int(k), int(segments), int(tile), workspace.data_ptr(),
+         workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr(),
+         _stream())
+    return vals, idx
+
+
+def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None):
+    """The k nearest gallery rows of every query -> (vals [Q, k] float32,
+    idx [Q, k] int32), ascending, ties by gallery index, (+inf, -1) past G
+    entries: exactly topk(compute_dist(q, gallery, math='h2'), k), from a
+    fused distance + top-k kernel (pps_search_h2_tiled) that never writes the
+    [Q, G] matrix.
+
+    gallery: a [G, D] tensor (indexed on the fly), a GalleryIndex, or a
+    sequence of GalleryIndex objects holding consecutive row segments of one
+    logical gallery (GalleryIndex.split: a gallery beyond one index's 2 GiB of
+    planes).  Each segment is searched on its own and the lists are merged
+    (topk_merge, in rounds when there are many); indices are global.
+    segments: gallery segments searched by independent workgroups (0 = auto);
+    tile: 0 .. search_num_tiles() - 1, same bits.  workspace: a device buffer
+    of search_workspace_bytes(Q, G, k, segments) bytes (G = the largest
+    segment) to reuse across calls; None allocates one.  All launches go on
+    the current stream.  Measured (DESIGN.md "Fused search"), it is slower than
+    the materialised path -- 1.25x at the Market shape, 1.04x at a 10,000 x
+    125,000 shard -- and peaks at 0.4 GB where that path holds a 5 GB matrix.
+
+    Falls back to compute_dist + topk -- which DOES materialise the [Q, G]
+    matrix -- when the fused kernel does not apply: an index holding an x3
+    split (also one the constructor downgraded from a requested 'h2'),
+    D % 32 != 0, non-contiguous queries (copied to whole rows first), or
+    k > search_max_k() (up to pps_topk's 1024)."""
+    if isinstance(gallery, GalleryIndex):
+        parts = [gallery]
+    elif isinstance(gallery, torch.Tensor):
+        g = gallery
+        h2ok = g.dim() == 2 and g.shape[1] % 32 == 0
+        parts = [GalleryIndex(g if g.is_contiguous() or not h2ok else g.contiguous(),
+                              math='h2' if h2ok else None)]
+    else:
+        parts = list(gallery)
+        if not parts or not all(isinstance(p, GalleryIndex) for p in parts):
+            raise RuntimeError('search: gallery must be a tensor, a GalleryIndex or a '
+                               'non-empty sequence of GalleryIndex')
+    if q.dim() != 2 or any(p.shape[1] != q.shape[1] for p in parts):
+        raise RuntimeError('search expects [Q, D] queries and [G, D] galleries')
+    k = int(k)
+    if k < 1:
+        raise RuntimeError('search: k must be >= 1')
+    D = q.shape[1]
+    if q.shape[0] == 0:
+        return (torch.empty((0, k), dtype=torch.float32, device=q.device),
+                torch.empty((0, k), dtype=torch.int32, device=q.device))
+    q_split = None
+    if (D % 32 == 0 and q.is_contiguous() and k <= search_max_k() and
+            any(p.h2 is not None for p in parts)):
+        q_split = split_h2_tiled(q)   # once, as compute_dist splits them
+    lists = [_search_one(q, q_split, p, k, metric, segments, tile, workspace) for p in parts]
+    if len(lists) == 1:
+        return lists[0]
+    offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])[:-1]]).astype(np.int64)
+    if offsets[-1] + parts[-1].shape[0] >= 2 ** 31:
+        raise RuntimeError('search: gallery indices must fit int32')
+    # merge rounds: each call takes at most R lists with R * k <= 8192, R <= 64;
+    # a merged list carries global indices (offset 0) into the next round
+    rmax = max(2, min(64, 8192 // k))
+    lists = [(v, i, int(o)) for (v, i), o in zip(lists, offsets)]
+    while len(lists) > 1:
+        nxt = []
+        for a in range(0, len(lists), rmax):
+            grp = lists[a:a + rmax]
+            if len(grp) == 1:
+                nxt.append(grp[0])
+                continue
+            v, i = topk_merge(torch.stack([g[0] for g in grp]), torch.stack([g[1] for g in grp]),
+                              [g[2] for g in grp], k)
+            nxt.append((v, i, 0))
+        lists = nxt
+    v, i, o = lists[0]
+    return v, i
 
 
 class MatchIndex(object):
