@@ -65,8 +65,6 @@ size_t rerank_workspace_bytes_for(const float*, int64_t, const float*, int64_t, 
                                   int64_t, int64_t, int64_t, int, int, int);
 int splitk_bn_act_normalize(const float*, int, int64_t, int, int, const float*,
                             const float*, int, int, float*, hipStream_t);
-int splitk_conv_epilogue(const float*, int, int64_t, int, const float*, const float*,
-                         const float*, int, float*, uint16_t*, int64_t, hipStream_t, float*);
 
 }  // namespace pps
 
@@ -595,194 +593,28 @@ int pps_conv1x1_seam_x3(const float* x, int64_t M, int K1, const uint16_t* w2c, 
   return launch_seam_x3(p, K1, N1, N2, as_stream(stream));
 }
 
-// weights either f32 [Cout][Kpad] (x3 = 0) or bf16x3 planes [3][Cout][Kpad]
-// x3p: bf16x3 activation planes (x_pl / y_pl, plane strides in elements)
-// instead of f32 x / y -- gemm_x3p.hip tiles only
-}  // extern "C"
-namespace pps {
-int conv_impl(const float* x, int N, int H, int W, int Cin, int ldx,
-                      const void* w, int x3, int Cout, int Kpad, int KH, int KW, int stride,
-                      int pad, int dil, const float* scale, const float* shift,
-                      const float* residual, int relu, float* y, int Ho, int Wo, int ldy,
-                      int tile, void* stream, const uint16_t* x_pl = nullptr,
-                      int64_t x_plane = 0, uint16_t* y_pl = nullptr, int64_t y_plane = 0,
-                      int splitk = 1, float* part = nullptr, int* fix_cnt = nullptr,
-                      int64_t n_cnt = 0, float* amax_out = nullptr,
-                      const float* w_rs = nullptr, const float* amax_in = nullptr,
-                      uint16_t* y_h2, int64_t y_h2_plane, const float* h2o_in, float h2o_bw,
-                      float h2o_bb) {
-  // y_h2: the output as f16x2 planes on the scale of the bound
-  // h2o_bw * max|x| + h2o_bb (EPI_F_H2OUT; the bound goes to amax_out)
-  PPS_ENFORCE((x != nullptr) != (x_pl != nullptr) &&
-                  (int)(y != nullptr) + (int)(y_pl != nullptr) + (int)(y_h2 != nullptr) == 1,
-              "exactly one of x / x planes and one of y / y planes / y f16x2 planes must be given");
-  if (y_h2) {
-    PPS_ENFORCE(relu && !residual && splitk == 1 && h2o_in && amax_out && x3 &&
-                    y_h2_plane >= (int64_t)N * Ho * Wo * ldy && Cin % 32 == 0 &&
-                    Kpad == KH * KW * Cin && h2o_bw >= 0.f && h2o_bb >= 0.f,
-                "f16x2 planes out: conv + BN + ReLU (no residual, no split-K), Cin % 32 == 0, "
-                "the input's slot, an output slot, a plane stride >= N*Ho*Wo*ldy");
-    y = reinterpret_cast<float*>(y_h2);  // for the shared checks below
-  }
-  // PPS_TILE_B_TILED or-ed into tile: the bf16x3 weights are chunk-tiled;
-  // PPS_TILE_COL_ORDER: column-major tile order
-  const bool wtiled = tile > 0 && (tile & PPS_TILE_B_TILED) != 0;
-  const bool colmajor = tile > 0 && (tile & PPS_TILE_COL_ORDER) != 0;
-  tile &= ~(PPS_TILE_B_TILED | PPS_TILE_COL_ORDER);
-  if (wtiled) {
-    PPS_ENFORCE(x3 && (splitk == 1 || fix_cnt), "tiled weights: bf16x3 weights, no two-pass split-K");
-    PPS_ENFORCE(Kpad % 32 == 0 && Cin % 32 == 0, "tiled weights need Cin % 32 == 0");
-    PPS_ENFORCE((tile >= GEMM_TILE_P_FIRST && tile < GEMM_TILE_WS) ||
-                    (tile > GEMM_TILE_WS && tile < GEMM_NUM_TILES),
-                "tiled weights need a pipelined tile (29..53, 55+)");
-  }
-  if (x_pl || y_pl) {
-    PPS_ENFORCE(x3, "activation planes need the bf16x3 weights");
-    PPS_ENFORCE(tile == 0 || tile >= GEMM_TILE_P_FIRST,
-                "activation planes need a pipelined tile (0 or >= " +
-                    std::to_string((int)GEMM_TILE_P_FIRST) + ")");
-    if (x_pl) x = reinterpret_cast<const float*>(x_pl);  // for the shared checks below
-    if (y_pl) y = reinterpret_cast<float*>(y_pl);
-    PPS_ENFORCE(!x_pl || x_plane >= (int64_t)N * H * W * ldx, "x plane stride too small");
-    PPS_ENFORCE(!y_pl || y_plane >= (int64_t)N * Ho * Wo * ldy, "y plane stride too small");
-  }
-  PPS_ENFORCE(x && w && scale && shift && y, "null pointer");
-  PPS_ENFORCE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "bad shape");
-  PPS_ENFORCE(Cin % 4 == 0 && ldx % 4 == 0 && ldx >= Cin,
-              "input channels must be a multiple of 4 (pad NHWC), got " +
-                  std::to_string(Cin));
-  PPS_ENFORCE(Kpad % 16 == 0 && Kpad >= KH * KW * Cin, "Kpad must be >= KH*KW*Cin, %16");
-  PPS_ENFORCE(stride >= 1 && dil >= 1 && pad >= 0, "bad stride/pad/dilation");
-  PPS_ENFORCE(Ho == (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1 &&
-                  Wo == (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1,
-              "output size does not match conv arithmetic");
-  PPS_ENFORCE(ldy >= Cout, "ldy < Cout");
-  PPS_ENFORCE(aligned16(x) && aligned16(w), "x/w must be 16-byte aligned");
-  PPS_ENFORCE((int64_t)N * Ho * Wo < (1ll << 31), "too many output pixels");
-  GemmParams p{};
-  p.splitk = 1;
-  PPS_ENFORCE(KH * KW <= 64, "at most 64 filter taps");
-  PPS_ENFORCE(Cin >= 16 || ((Cin & (Cin - 1)) == 0 && Kpad <= 64 * Cin),
-              "channels < 16 must be a power of two with Kpad <= 64*Cin");
-  PPS_ENFORCE((int64_t)N * H * W * ldx * 4 < kMaxBufBytes, "input larger than 2 GiB");
-  PPS_ENFORCE((int64_t)Cout * Kpad * 6 < kMaxBufBytes, "weights larger than 2 GiB");
-  p.a = x; p.H = H; p.W = W; p.Cin = Cin; p.lda = ldx;
-  p.a_bytes = (uint32_t)((int64_t)N * H * W * ldx * 4);
-  p.b_bytes = (uint32_t)((int64_t)Cout * Kpad * 4);
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
-  p.Ho = Ho; p.Wo = Wo; p.M = N * Ho * Wo;
-  p.ldb = Kpad; p.kb_valid = Kpad; p.Ncol = Cout; p.Kloop = Kpad;
-  p.scale = scale; p.shift = shift; p.residual = residual; p.ldr = ldy;
-  p.out = y; p.ldo = ldy; p.relu = relu; p.tile = tile;
-  p.colmajor = colmajor ? 1 : 0;
-  p.amax_out = amax_out;
-  int h2o = 0;
-  if (y_h2) {
-    p.out = nullptr; p.out3 = y_h2; p.out_plane = y_h2_plane;
-    p.h2o_in = h2o_in; p.h2o_bw = h2o_bw; p.h2o_bb = h2o_bb;
-    h2o = EPI_F_H2OUT;
-  }
-  if (w_rs) {
-    // f16x2 (pps_conv2d_bn_act_h2, the whole-network plan's PPS_TILE_H2):
-    // f32 activations scaled by their tensor's max, chunk-tiled two-plane
-    // weights [2][Cout16 / 16][Kpad / 32][16][32] with per-channel scales
-    // x_pl: f16x2 activation planes [2][x_plane] (pps_split_f16x2_act of x
-    // with the same max): same bits as the f32 input, no split in the loop
-    PPS_ENFORCE(!y_pl && splitk == 1, "f16x2 conv: f32 output, no split-K");
-    PPS_ENFORCE(amax_in != nullptr, "f16x2 conv: the input tensor's max (amax_x) is required");
-    PPS_ENFORCE(Cin % 32 == 0 && Kpad == KH * KW * Cin,
-                "f16x2 conv: Cin % 32 == 0 and Kpad == KH*KW*Cin");
-    PPS_ENFORCE(tile == 0 || (tile >= GEMM_TILE_P16_FIRST && tile < GEMM_NUM_TILES),
-                "f16x2 conv: tile 0 or 38..60 (54: the weight-stationary 1x1 where it "
-                "applies, else 38)");
-    p.b3 = static_cast<const uint16_t*>(w);
-    p.b_plane = (int64_t)(Cout + 15) / 16 * 16 * Kpad;
-    p.b_bytes = (uint32_t)(p.b_plane * 2);
-    p.tiled = 2;
-    p.rs_b = w_rs;
-    p.amax_a = amax_in;
-    if (x_pl) {
-      p.a = nullptr; p.a3 = x_pl; p.a_plane = x_plane;
-      p.a_bytes = (uint32_t)((int64_t)N * H * W * ldx * 2);
-    }
-    return launch_gemm_x3(p, EPI_CONV | EPI_F_H2 | h2o, 1, as_stream(stream));
-  }
-  if (x_pl) {
-    p.a = nullptr; p.a3 = x_pl; p.a_plane = x_plane;
-    p.a_bytes = (uint32_t)((int64_t)N * H * W * ldx * 2);
-  }
-  if (splitk > 1) {
-    // conv split-K: raw partial sums of K slices [splitk][M][Cout] on the
-    // pipelined kernel, then one pass that sums them in slice order and
-    // applies BN [+ residual] [ReLU] (f32 or bf16x3-plane output)
-    PPS_ENFORCE(x3 && part, "split-K needs the bf16x3 weights and a partials buffer");
-    PPS_ENFORCE(Cin % 32 == 0 && Kpad % (32 * splitk) == 0 && Kpad == KH * KW * Cin,
-                "split-K needs Cin % 32 == 0 and Kpad % (32 * splitk) == 0");
-    PPS_ENFORCE(ldy == Cout && Cout % 4 == 0 && aligned16(part), "split-K: dense output");
-    PPS_ENFORCE(tile == 0 || tile >= GEMM_TILE_P_FIRST, "split-K needs a pipelined tile");
-    const int64_t M = (int64_t)N * Ho * Wo;
-    p.splitk = splitk; p.ksplit_conv = 1;
-    p.Kloop = Kpad / splitk; p.kb_valid = p.Kloop;
-    p.b3 = static_cast<const uint16_t*>(w); p.b_plane = (int64_t)Cout * Kpad;
-    p.b_bytes = (uint32_t)(p.b_plane * 2);
-    if (fix_cnt) {
-      // one launch: the last K slice of each tile to finish sums the parked
-      // partials (slice order) and runs BN [+ residual] + ReLU [-> planes]
-      PPS_ENFORCE(relu, "one-launch split-K: conv + BN + ReLU epilogues only");
-      PPS_ENFORCE(!(residual && y_pl), "one-launch split-K: residual with f32 output only");
-      const int t = tile ? tile : GEMM_TILE_P16_FIRST + 7;
-      const int bm = x3p_tile_rows(t, x_pl != nullptr), bn = x3p_tile_cols(t, x_pl != nullptr);
-      PPS_ENFORCE(bm > 0 && bn > 0, "one-launch split-K needs a pipelined tile");
-      const int64_t ntile = ((M + bm - 1) / bm) * ((Cout + bn - 1) / bn);
-      PPS_ENFORCE(n_cnt >= ntile, "one-launch split-K: " + std::to_string(ntile) +
-                                      " tile counters needed, " + std::to_string(n_cnt) + " given");
-      if (wtiled) {
-        p.b_plane = (int64_t)(Cout + 15) / 16 * 16 * Kpad;
-        p.tiled = 2;
-        p.b_bytes = (uint32_t)(p.b_plane * 2);
-      }
-      p.tile = t;
-      p.part = part; p.part_sstride = M * Cout; p.fix_cnt = fix_cnt;
-      p.out_sstride = 0;
-      if (y_pl) { p.out = nullptr; p.out3 = y_pl; p.out_plane = y_plane; }
-      return launch_gemm_x3(p, (y_pl ? EPI_CONV | EPI_F_PLANES : EPI_CONV) | EPI_F_FIX, 1,
-                            as_stream(stream));
-    }
-    p.out = part; p.out3 = nullptr; p.ldo = Cout; p.out_sstride = M * Cout;
-    p.residual = nullptr; p.relu = 0;
-    // tile 0: tile 45, the one-launch entry's default (same rounding group,
-    // so both entries give the same bits at tile 0 as at any equal id)
-    p.tile = tile ? tile : GEMM_TILE_P16_FIRST + 7;
-    const int rc = launch_gemm_x3(p, EPI_CONV | EPI_F_RAW, 1, as_stream(stream));
-    if (rc != PPS_OK) return rc;
-    return splitk_conv_epilogue(part, splitk, M, Cout, scale, shift, residual, relu,
-                                y_pl ? nullptr : y, y_pl, y_plane, as_stream(stream), amax_out);
-  }
-  if (y_pl) { p.out = nullptr; p.out3 = y_pl; p.out_plane = y_plane; }
-  if (x3) {
-    p.b3 = static_cast<const uint16_t*>(w); p.b_plane = (int64_t)Cout * Kpad;
-    if (wtiled) {  // [3][Cout16 / 16][Kpad / 32][16][32]
-      p.b_plane = (int64_t)(Cout + 15) / 16 * 16 * Kpad;
-      p.tiled = 2;
-    }
-    p.b_bytes = (uint32_t)(p.b_plane * 2);
-    PPS_ENFORCE(!h2o || !x_pl, "f16x2 planes out from a bf16x3 conv: f32 activations in");
-    return launch_gemm_x3(p, (y_pl ? EPI_CONV | EPI_F_PLANES : EPI_CONV) | h2o, 1,
-                          as_stream(stream));
-  }
-  p.b = static_cast<const float*>(w);
-  return launch_gemm(p, EPI_CONV, 1, as_stream(stream));
-}
-}  // namespace pps
-extern "C" {
+// ---- convolutions: the implementations are conv_ops.hip's conv_impl /
+// conv_pps_impl / dual_impl; an entry point names what it was given ----------
+#define PPS_CONV_SHAPE(a)                                                            \
+  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ldx = ldx; a.Cout = Cout; a.Kpad = Kpad; \
+  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dil;                 \
+  a.scale = scale; a.shift = shift; a.Ho = Ho; a.Wo = Wo; a.tile = tile; a.stream = stream
+#define PPS_DUAL_SHAPE(a)                                                                 \
+  a.x = x; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ldx = ldx; a.KH = KH; a.KW = KW;     \
+  a.stride = stride; a.pad = pad; a.x2 = x2; a.H2 = H2; a.W2 = W2; a.Cin2 = Cin2;         \
+  a.ldx2 = ldx2; a.stride2 = stride2; a.Cout = Cout; a.Kpad = Kpad1; a.Kpad2 = Kpad2;     \
+  a.shift = shift; a.relu = relu; a.y = y; a.Ho = Ho; a.Wo = Wo; a.ldy = ldy;             \
+  a.tile = tile; a.stream = stream
 
 int pps_conv2d_bn_act(const float* x, int N, int H, int W, int Cin, int ldx,
                       const float* w, int Cout, int Kpad, int KH, int KW, int stride,
                       int pad, int dil, const float* scale, const float* shift,
                       const float* residual, int relu, float* y, int Ho, int Wo, int ldy,
                       int tile, void* stream) {
-  return conv_impl(x, N, H, W, Cin, ldx, w, 0, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.w = w; a.residual = residual; a.relu = relu; a.y = y; a.ldy = ldy;
+  return conv_impl(a);
 }
 
 int pps_conv2d_bn_act_x3(const float* x, int N, int H, int W, int Cin, int ldx,
@@ -790,8 +622,25 @@ int pps_conv2d_bn_act_x3(const float* x, int N, int H, int W, int Cin, int ldx,
                          int pad, int dil, const float* scale, const float* shift,
                          const float* residual, int relu, float* y, int Ho, int Wo, int ldy,
                          int tile, void* stream) {
-  return conv_impl(x, N, H, W, Cin, ldx, w3, 1, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.w = w3; a.x3 = 1; a.residual = residual; a.relu = relu; a.y = y; a.ldy = ldy;
+  return conv_impl(a);
+}
+
+// x3p: bf16x3 activation planes (x3 / y3, plane strides in elements) instead
+// of f32 x / y
+int pps_conv2d_bn_act_x3p(const float* x, const uint16_t* x3, int64_t x_plane, int N, int H,
+                          int W, int Cin, int ldx, const uint16_t* w3, int Cout, int Kpad,
+                          int KH, int KW, int stride, int pad, int dil, const float* scale,
+                          const float* shift, const float* residual, int relu, float* y,
+                          uint16_t* y3, int64_t y_plane, int Ho, int Wo, int ldy, int tile,
+                          void* stream) {
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.x_pl = x3; a.x_plane = x_plane; a.w = w3; a.x3 = 1;
+  a.residual = residual; a.relu = relu; a.y = y; a.y_pl = y3; a.y_plane = y_plane; a.ldy = ldy;
+  return conv_impl(a);
 }
 
 int pps_conv2d_bn_act_x3p_splitk(const float* x, const uint16_t* x3, int64_t x_plane, int N,
@@ -802,9 +651,12 @@ int pps_conv2d_bn_act_x3p_splitk(const float* x, const uint16_t* x3, int64_t x_p
                                  int Wo, int ldy, int splitk, float* part, int tile,
                                  void* stream) {
   PPS_ENFORCE(splitk >= 1 && splitk <= 16, "splitk must be in [1, 16]");
-  return conv_impl(x, N, H, W, Cin, ldx, w3, 1, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream, x3, x_plane, y3,
-                   y_plane, splitk, part);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.x_pl = x3; a.x_plane = x_plane; a.w = w3; a.x3 = 1;
+  a.residual = residual; a.relu = relu; a.y = y; a.y_pl = y3; a.y_plane = y_plane; a.ldy = ldy;
+  a.splitk = splitk; a.part = part;
+  return conv_impl(a);
 }
 
 int pps_conv2d_bn_act_x3p_splitk_fused(const float* x, const uint16_t* x3, int64_t x_plane,
@@ -817,20 +669,12 @@ int pps_conv2d_bn_act_x3p_splitk_fused(const float* x, const uint16_t* x3, int64
                                        void* stream) {
   PPS_ENFORCE(splitk >= 2 && splitk <= 16, "splitk must be in [2, 16]");
   PPS_ENFORCE(counters != nullptr, "null tile counters");
-  return conv_impl(x, N, H, W, Cin, ldx, w3, 1, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream, x3, x_plane, y3,
-                   y_plane, splitk, part, counters, n_counters);
-}
-
-int pps_conv2d_bn_act_x3p(const float* x, const uint16_t* x3, int64_t x_plane, int N, int H,
-                          int W, int Cin, int ldx, const uint16_t* w3, int Cout, int Kpad,
-                          int KH, int KW, int stride, int pad, int dil, const float* scale,
-                          const float* shift, const float* residual, int relu, float* y,
-                          uint16_t* y3, int64_t y_plane, int Ho, int Wo, int ldy, int tile,
-                          void* stream) {
-  return conv_impl(x, N, H, W, Cin, ldx, w3, 1, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream, x3, x_plane, y3,
-                   y_plane);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.x_pl = x3; a.x_plane = x_plane; a.w = w3; a.x3 = 1;
+  a.residual = residual; a.relu = relu; a.y = y; a.y_pl = y3; a.y_plane = y_plane; a.ldy = ldy;
+  a.splitk = splitk; a.part = part; a.fix_cnt = counters; a.n_cnt = n_counters;
+  return conv_impl(a);
 }
 
 int pps_x3p_tile_shape(int tile, int planes, int* rows, int* cols) {
@@ -841,92 +685,18 @@ int pps_x3p_tile_shape(int tile, int planes, int* rows, int* cols) {
 }
 
 // The last res5 conv with the part pooling fused into its epilogue
-// (ResNet.py:276-333 res5_2 branch2c + Sum + Relu, then bpm_heads.py:18-55 /
-// pps_heads.py:38-80): conv + BN + residual + ReLU on a pipelined tile whose
-// rows are exactly one image (Ho * Wo); each tile pools its image's strips
-// and writes the 2^S - 1 part subsets into pps_out [2^S - 1][N][Cout] as
-// pps_part_power_set does (same bits).  y (the conv output) may be null: it
-// is then never written.
-}  // extern "C"
-namespace pps {
-int conv_pps_impl(const float* x, const uint16_t* x3, int64_t x_plane, int N,
-                              int H, int W, int Cin, int ldx, const uint16_t* w3, int Cout,
-                              int Kpad, int KH, int KW, int stride, int pad, int dil,
-                              const float* scale, const float* shift, const float* residual,
-                              float* y, int Ho, int Wo, const int32_t* splits, int S,
-                              int max_ave, float* pps_out, int tile, void* stream,
-                              const float* w_rs, const float* amax_in) {
-  PPS_ENFORCE((x != nullptr) != (x3 != nullptr), "exactly one of x / x planes must be given");
-  PPS_ENFORCE(w3 && scale && shift && residual && pps_out && splits, "null pointer");
-  PPS_ENFORCE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 4 == 0, "bad shape");
-  PPS_ENFORCE(Cin % 32 == 0 && ldx % 8 == 0 && ldx >= Cin && Kpad == KH * KW * Cin,
-              "pipelined conv: Cin % 32 == 0, Kpad == KH*KW*Cin");
-  PPS_ENFORCE(KH * KW <= 64 && stride >= 1 && dil >= 1 && pad >= 0, "bad filter");
-  PPS_ENFORCE(Ho == (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1 &&
-                  Wo == (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1,
-              "output size does not match conv arithmetic");
-  PPS_ENFORCE(S >= 1 && S <= kPpsFuseMaxStrips, "1..10 strips");
-  int hsum = 0;
-  for (int j = 0; j < S; ++j) {
-    PPS_ENFORCE(splits[j] > 0, "strip heights must be positive");
-    hsum += splits[j];
-  }
-  PPS_ENFORCE(hsum == Ho, "strip heights must sum to the output height");
-  const bool pl = x3 != nullptr;
-  // chunk-tiled weights (always for f16x2: two planes, per-channel scales)
-  const bool wtiled = w_rs != nullptr || (tile > 0 && (tile & PPS_TILE_B_TILED) != 0);
-  PPS_ENFORCE(!w_rs || amax_in, "f16x2: the activations' max is required");
-  const bool colmajor = tile > 0 && (tile & PPS_TILE_COL_ORDER) != 0;
-  tile &= ~(PPS_TILE_B_TILED | PPS_TILE_COL_ORDER);
-  if (tile == 0) tile = pl ? GEMM_TILE_P16_FIRST + 1 : GEMM_TILE_P16_192x128W42;
-  PPS_ENFORCE(!w_rs || tile >= GEMM_TILE_P16_FIRST, "f16x2: a 16x16x32 tile (38+)");
-  PPS_ENFORCE(x3p_tile_rows(tile, pl) == Ho * Wo && x3p_tile_cols(tile, pl) <= kPpsFuseMaxCols,
-              "the fused pooling needs a pipelined tile of exactly Ho*Wo = " +
-                  std::to_string(Ho * Wo) + " rows and <= 256 columns, tile " +
-                  std::to_string(tile) + " has " + std::to_string(x3p_tile_rows(tile, pl)));
-  PPS_ENFORCE((int64_t)N * H * W * ldx * (pl ? 2 : 4) < kMaxBufBytes, "input larger than 2 GiB");
-  PPS_ENFORCE((int64_t)(1 << S) * N * Cout < (1ll << 31), "part output too large");
-  PPS_ENFORCE(aligned16(pl ? (const void*)x3 : (const void*)x) && aligned16(w3) &&
-                  aligned16(scale) && aligned16(shift) && aligned16(residual) &&
-                  (!y || aligned16(y)),
-              "16-byte aligned pointers");
-  PPS_ENFORCE(!pl || x_plane >= (int64_t)N * H * W * ldx, "x plane stride too small");
-  GemmParams p{};
-  p.splitk = 1;
-  p.a = x; p.H = H; p.W = W; p.Cin = Cin; p.lda = ldx;
-  p.a_bytes = (uint32_t)((int64_t)N * H * W * ldx * (pl ? 2 : 4));
-  if (pl) { p.a = nullptr; p.a3 = x3; p.a_plane = x_plane; }
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
-  p.Ho = Ho; p.Wo = Wo; p.M = N * Ho * Wo;
-  p.ldb = Kpad; p.kb_valid = Kpad; p.Ncol = Cout; p.Kloop = Kpad;
-  p.b3 = w3; p.b_plane = (int64_t)(wtiled ? (Cout + 15) / 16 * 16 : Cout) * Kpad;
-  p.b_bytes = (uint32_t)(p.b_plane * 2);
-  p.tiled = wtiled ? 2 : 0;
-  p.colmajor = colmajor ? 1 : 0;
-  p.scale = scale; p.shift = shift; p.residual = residual; p.ldr = Cout;
-  p.out = y; p.ldo = Cout; p.relu = 1; p.tile = tile;
-  p.pps_out = pps_out; p.pps_S = S; p.pps_max_ave = max_ave ? 1 : 0; p.pps_nimg = N;
-  p.pps_write_y = y ? 1 : 0;
-  for (int j = 0; j < S; ++j) p.pps_h[j] = splits[j];
-  PPS_ENFORCE(x3p_eligible(p, EPI_CONV | EPI_F_RES | EPI_F_RELU), "shape not eligible for the pipelined GEMM");
-  const int h2 = w_rs ? EPI_F_H2 : 0;
-  p.rs_b = w_rs;
-  p.amax_a = amax_in;
-  return launch_gemm_x3p(p, EPI_CONV | EPI_F_RES | EPI_F_RELU | EPI_F_PPS | h2, 1,
-                         as_stream(stream), tile - GEMM_TILE_P_FIRST);
-}
-}  // namespace pps
-extern "C" {
-
+// (conv_ops.hip conv_pps_impl)
 int pps_conv2d_bn_act_pps_x3p(const float* x, const uint16_t* x3, int64_t x_plane, int N,
                               int H, int W, int Cin, int ldx, const uint16_t* w3, int Cout,
                               int Kpad, int KH, int KW, int stride, int pad, int dil,
                               const float* scale, const float* shift, const float* residual,
                               float* y, int Ho, int Wo, const int32_t* splits, int S,
                               int max_ave, float* pps_out, int tile, void* stream) {
-  return conv_pps_impl(x, x3, x_plane, N, H, W, Cin, ldx, w3, Cout, Kpad, KH, KW, stride, pad,
-                       dil, scale, shift, residual, y, Ho, Wo, splits, S, max_ave, pps_out, tile,
-                       stream, nullptr, nullptr);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.x_pl = x3; a.x_plane = x_plane; a.w = w3; a.x3 = 1; a.residual = residual; a.y = y;
+  a.splits = splits; a.S = S; a.max_ave = max_ave; a.pps_out = pps_out;
+  return conv_pps_impl(a);
 }
 
 // ---- f16x2 convolutions (include/pps_abi.h "f16x2 convolutions") ----------
@@ -937,9 +707,11 @@ int pps_conv2d_bn_act_h2(const float* x, int N, int H, int W, int Cin, int ldx,
                          int Wo, int ldy, const float* amax_x, float* amax_y, int tile,
                          void* stream) {
   PPS_ENFORCE(wrs != nullptr, "null weight scales");
-  return conv_impl(x, N, H, W, Cin, ldx, w2t, 1, Cout, Kpad, KH, KW, stride, pad, dil, scale,
-                   shift, residual, relu, y, Ho, Wo, ldy, tile, stream, nullptr, 0, nullptr, 0, 1,
-                   nullptr, nullptr, 0, amax_y, wrs, amax_x);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.w = w2t; a.x3 = 1; a.w_rs = wrs; a.residual = residual; a.relu = relu;
+  a.y = y; a.ldy = ldy; a.amax_in = amax_x; a.amax_out = amax_y;
+  return conv_impl(a);
 }
 
 int pps_conv2d_dual_bn_act_h2(const float* x, int N, int H, int W, int Cin, int ldx, int KH,
@@ -950,9 +722,11 @@ int pps_conv2d_dual_bn_act_h2(const float* x, int N, int H, int W, int Cin, int 
                               const float* amax_x, const float* amax_x2, float* amax_y, int tile,
                               void* stream) {
   PPS_ENFORCE(wrs != nullptr, "null weight scales");
-  return dual_impl(x, N, H, W, Cin, ldx, KH, KW, stride, pad, x2, H2, W2, Cin2, ldx2, stride2,
-                   w2t, 1, Cout, Kpad1, Kpad2, shift, relu, y, Ho, Wo, ldy, tile, stream, amax_y,
-                   wrs, amax_x, amax_x2);
+  DualArgs a;
+  PPS_DUAL_SHAPE(a);
+  a.w = w2t; a.x3 = 1; a.w_rs = wrs;
+  a.amax_in = amax_x; a.amax_in2 = amax_x2; a.amax_out = amax_y;
+  return dual_impl(a);
 }
 
 int pps_conv2d_bn_act_h2_planes(const uint16_t* x2, int64_t x_plane, int N, int H, int W,
@@ -962,9 +736,12 @@ int pps_conv2d_bn_act_h2_planes(const uint16_t* x2, int64_t x_plane, int N, int 
                                 int relu, float* y, int Ho, int Wo, int ldy, const float* amax_x,
                                 float* amax_y, int tile, void* stream) {
   PPS_ENFORCE(wrs != nullptr && x2 != nullptr, "null pointer");
-  return conv_impl(nullptr, N, H, W, Cin, ldx, w2t, 1, Cout, Kpad, KH, KW, stride, pad, dil,
-                   scale, shift, residual, relu, y, Ho, Wo, ldy, tile, stream, x2, x_plane,
-                   nullptr, 0, 1, nullptr, nullptr, 0, amax_y, wrs, amax_x);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x_pl = x2; a.x_plane = x_plane; a.w = w2t; a.x3 = 1; a.w_rs = wrs;
+  a.residual = residual; a.relu = relu; a.y = y; a.ldy = ldy;
+  a.amax_in = amax_x; a.amax_out = amax_y;
+  return conv_impl(a);
 }
 
 int pps_conv2d_bn_act_h2out(const float* x, const uint16_t* x2, int64_t x_plane, int N, int H,
@@ -976,10 +753,13 @@ int pps_conv2d_bn_act_h2out(const float* x, const uint16_t* x2, int64_t x_plane,
                             void* stream) {
   PPS_ENFORCE(w && y2 && bound_in && bound_out, "null pointer");
   PPS_ENFORCE(!x2 || wrs, "f16x2 activation planes in: f16x2 weights (wrs) only");
-  return conv_impl(x2 ? nullptr : x, N, H, W, Cin, ldx, w, 1, Cout, Kpad, KH, KW, stride, pad,
-                   dil, scale, shift, nullptr, 1, nullptr, Ho, Wo, ldy, tile, stream, x2, x_plane,
-                   nullptr, 0, 1, nullptr, nullptr, 0, bound_out, wrs, wrs ? amax_x : nullptr, y2,
-                   y_plane, bound_in, bound_w, bound_b);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x2 ? nullptr : x; a.x_pl = x2; a.x_plane = x_plane; a.w = w; a.x3 = 1; a.w_rs = wrs;
+  a.relu = 1; a.y_h2 = y2; a.y_h2_plane = y_plane; a.ldy = ldy;
+  a.amax_in = wrs ? amax_x : nullptr; a.amax_out = bound_out;
+  a.h2o_in = bound_in; a.h2o_bw = bound_w; a.h2o_bb = bound_b;
+  return conv_impl(a);
 }
 
 int pps_conv2d_bn_act_pps_h2_planes(const uint16_t* x2, int64_t x_plane, int N, int H, int W,
@@ -990,9 +770,12 @@ int pps_conv2d_bn_act_pps_h2_planes(const uint16_t* x2, int64_t x_plane, int N, 
                                     const int32_t* splits, int S, int max_ave, float* pps_out,
                                     const float* amax_x, int tile, void* stream) {
   PPS_ENFORCE(wrs != nullptr && x2 != nullptr, "null pointer");
-  return conv_pps_impl(nullptr, x2, x_plane, N, H, W, Cin, ldx, w2t, Cout, Kpad, KH, KW, stride,
-                       pad, dil, scale, shift, residual, y, Ho, Wo, splits, S, max_ave, pps_out,
-                       tile, stream, wrs, amax_x);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x_pl = x2; a.x_plane = x_plane; a.w = w2t; a.x3 = 1; a.w_rs = wrs; a.residual = residual;
+  a.y = y; a.splits = splits; a.S = S; a.max_ave = max_ave; a.pps_out = pps_out;
+  a.amax_in = amax_x;
+  return conv_pps_impl(a);
 }
 
 int pps_conv2d_bn_act_pps_h2(const float* x, int N, int H, int W, int Cin, int ldx,
@@ -1002,96 +785,23 @@ int pps_conv2d_bn_act_pps_h2(const float* x, int N, int H, int W, int Cin, int l
                              const int32_t* splits, int S, int max_ave, float* pps_out,
                              const float* amax_x, int tile, void* stream) {
   PPS_ENFORCE(wrs != nullptr, "null weight scales");
-  return conv_pps_impl(x, nullptr, 0, N, H, W, Cin, ldx, w2t, Cout, Kpad, KH, KW, stride, pad,
-                       dil, scale, shift, residual, y, Ho, Wo, splits, S, max_ave, pps_out, tile,
-                       stream, wrs, amax_x);
+  ConvArgs a;
+  PPS_CONV_SHAPE(a);
+  a.x = x; a.w = w2t; a.x3 = 1; a.w_rs = wrs; a.residual = residual;
+  a.y = y; a.splits = splits; a.S = S; a.max_ave = max_ave; a.pps_out = pps_out;
+  a.amax_in = amax_x;
+  return conv_pps_impl(a);
 }
-
-}  // extern "C"
-namespace pps {
-int dual_impl(const float* x, int N, int H, int W, int Cin, int ldx,
-                           int KH, int KW, int stride, int pad, const float* x2, int H2,
-                           int W2, int Cin2, int ldx2, int stride2, const void* w, int x3,
-                           int Cout, int Kpad1, int Kpad2, const float* shift, int relu,
-                           float* y, int Ho, int Wo, int ldy, int tile, void* stream,
-                           float* amax_out, const float* w_rs, const float* amax_in,
-                           const float* amax_in2) {
-  PPS_ENFORCE(x && x2 && w && shift && y, "null pointer");
-  PPS_ENFORCE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin2 > 0, "bad shape");
-  const bool wtiled = tile > 0 && (tile & PPS_TILE_B_TILED) != 0;  // chunk-tiled weights
-  const bool colmajor = tile > 0 && (tile & PPS_TILE_COL_ORDER) != 0;
-  tile &= ~(PPS_TILE_B_TILED | PPS_TILE_COL_ORDER);
-  if (wtiled)
-    PPS_ENFORCE(x3 && (Kpad1 + Kpad2) % 32 == 0 &&
-                    ((tile >= GEMM_TILE_P_FIRST && tile < GEMM_TILE_WS) ||
-                     (tile > GEMM_TILE_WS && tile < GEMM_NUM_TILES)),
-                "tiled weights: bf16x3, K % 32 == 0, a pipelined tile");
-  PPS_ENFORCE(Cin % 4 == 0 && ldx % 4 == 0 && Cin2 % 16 == 0 && ldx2 % 4 == 0,
-              "channel counts must be multiples of 4 (second operand: 16)");
-  PPS_ENFORCE(Kpad1 % 16 == 0 && Kpad1 >= KH * KW * Cin && Kpad2 == Cin2,
-              "Kpad1 >= KH*KW*Cin (%16), Kpad2 == Cin2");
-  PPS_ENFORCE(KH * KW <= 64, "at most 64 filter taps");
-  PPS_ENFORCE(Ho == (H + 2 * pad - (KH - 1) - 1) / stride + 1 &&
-                  Wo == (W + 2 * pad - (KW - 1) - 1) / stride + 1,
-              "output size does not match conv arithmetic");
-  PPS_ENFORCE(Ho == (H2 - 1) / stride2 + 1 && Wo == (W2 - 1) / stride2 + 1,
-              "second operand (1x1, stride2) does not map onto the output grid");
-  PPS_ENFORCE((int64_t)N * H * W * ldx * 4 < kMaxBufBytes &&
-                  (int64_t)N * H2 * W2 * ldx2 * 4 < kMaxBufBytes,
-              "input larger than 2 GiB");
-  PPS_ENFORCE(aligned16(x) && aligned16(x2) && aligned16(w), "16-byte alignment");
-  GemmParams p{};
-  p.splitk = 1;
-  p.a = x; p.H = H; p.W = W; p.Cin = Cin; p.lda = ldx;
-  p.a_bytes = (uint32_t)((int64_t)N * H * W * ldx * 4);
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = 1;
-  p.Ho = Ho; p.Wo = Wo; p.M = N * Ho * Wo;
-  p.a2 = x2; p.a2_bytes = (uint32_t)((int64_t)N * H2 * W2 * ldx2 * 4);
-  p.H2 = H2; p.W2 = W2; p.lda2 = ldx2; p.stride2 = stride2; p.Kloop1 = Kpad1;
-  p.ldb = Kpad1 + Kpad2; p.kb_valid = Kpad1 + Kpad2; p.Ncol = Cout;
-  p.Kloop = Kpad1 + Kpad2;
-  p.scale = nullptr; p.shift = shift; p.out = y; p.ldo = ldy; p.relu = relu; p.tile = tile;
-  p.colmajor = colmajor ? 1 : 0;
-  PPS_ENFORCE((int64_t)Cout * (Kpad1 + Kpad2) * 6 < kMaxBufBytes, "weights larger than 2 GiB");
-  p.amax_out = amax_out;
-  if (w_rs) {  // f16x2: both operands share their maxima's scale (conv_impl)
-    PPS_ENFORCE(amax_in && amax_in2, "f16x2 conv: both inputs' maxima are required");
-    PPS_ENFORCE(Cin % 32 == 0 && Kpad1 == KH * KW * Cin && Kpad2 % 32 == 0,
-                "f16x2 conv: Cin % 32 == 0, Kpad1 == KH*KW*Cin, Cin2 % 32 == 0");
-    PPS_ENFORCE(tile == 0 || tile == GEMM_TILE_P16_192x128W41 ||
-                    (tile >= GEMM_TILE_P16_FIRST && tile < GEMM_TILE_C16_FIRST),
-                "f16x2 fused-shortcut conv: tile 0, 38..55 or 60");
-    p.b3 = static_cast<const uint16_t*>(w);
-    p.b_plane = (int64_t)(Cout + 15) / 16 * 16 * (Kpad1 + Kpad2);
-    p.b_bytes = (uint32_t)(p.b_plane * 2);
-    p.tiled = 2;
-    p.rs_b = w_rs;
-    p.amax_a = amax_in;
-    p.amax_a2 = amax_in2;
-    return launch_gemm_x3(p, EPI_CONV | EPI_F_H2, 1, as_stream(stream));
-  }
-  if (x3) {
-    p.b3 = static_cast<const uint16_t*>(w);
-    p.b_plane = (int64_t)(wtiled ? (Cout + 15) / 16 * 16 : Cout) * (Kpad1 + Kpad2);
-    p.b_bytes = (uint32_t)(p.b_plane * 2);
-    p.tiled = wtiled ? 2 : 0;
-    return launch_gemm_x3(p, EPI_CONV, 1, as_stream(stream));
-  }
-  p.b = static_cast<const float*>(w);
-  p.b_bytes = (uint32_t)((int64_t)Cout * (Kpad1 + Kpad2) * 4);
-  return launch_gemm(p, EPI_CONV, 1, as_stream(stream));
-}
-}  // namespace pps
-extern "C" {
 
 int pps_conv2d_dual_bn_act(const float* x, int N, int H, int W, int Cin, int ldx,
                            int KH, int KW, int stride, int pad, const float* x2, int H2,
                            int W2, int Cin2, int ldx2, int stride2, const float* w,
                            int Cout, int Kpad1, int Kpad2, const float* shift, int relu,
                            float* y, int Ho, int Wo, int ldy, int tile, void* stream) {
-  return dual_impl(x, N, H, W, Cin, ldx, KH, KW, stride, pad, x2, H2, W2, Cin2, ldx2, stride2,
-                   w, 0, Cout, Kpad1, Kpad2, shift, relu, y, Ho, Wo, ldy, tile, stream, nullptr,
-                   nullptr, nullptr, nullptr);
+  DualArgs a;
+  PPS_DUAL_SHAPE(a);
+  a.w = w;
+  return dual_impl(a);
 }
 
 int pps_conv2d_dual_bn_act_x3(const float* x, int N, int H, int W, int Cin, int ldx,
@@ -1099,10 +809,13 @@ int pps_conv2d_dual_bn_act_x3(const float* x, int N, int H, int W, int Cin, int 
                               int W2, int Cin2, int ldx2, int stride2, const uint16_t* w3,
                               int Cout, int Kpad1, int Kpad2, const float* shift, int relu,
                               float* y, int Ho, int Wo, int ldy, int tile, void* stream) {
-  return dual_impl(x, N, H, W, Cin, ldx, KH, KW, stride, pad, x2, H2, W2, Cin2, ldx2, stride2,
-                   w3, 1, Cout, Kpad1, Kpad2, shift, relu, y, Ho, Wo, ldy, tile, stream, nullptr,
-                   nullptr, nullptr, nullptr);
+  DualArgs a;
+  PPS_DUAL_SHAPE(a);
+  a.w = w3; a.x3 = 1;
+  return dual_impl(a);
 }
+#undef PPS_CONV_SHAPE
+#undef PPS_DUAL_SHAPE
 
 int pps_gemm_bn_act_batched(const float* x, int64_t x_bstride, int M, int K,
                             const float* w, int64_t w_bstride, int Cout,
@@ -1127,34 +840,6 @@ int pps_gemm_bn_act_batched(const float* x, int64_t x_bstride, int M, int K,
   p.scale = scale; p.shift = shift; p.ss_bstride = Cout;
   p.out = y; p.ldo = ldy; p.out_bstride = Cout; p.relu = relu; p.tile = tile;
   return launch_gemm(p, EPI_CONV, B, as_stream(stream));
-}
-
-static int splitk_impl(const float* x, int M, int K, const void* w, int x3, int Cout, int B,
-                            int splitk, float* part, int tile, void* stream) {
-  PPS_ENFORCE(x && w && part, "null pointer");
-  PPS_ENFORCE(M > 0 && K > 0 && Cout > 0 && B > 0 && splitk >= 1, "bad shape");
-  PPS_ENFORCE(K % (16 * splitk) == 0, "K must be a multiple of 16*splitk");
-  PPS_ENFORCE((int64_t)M * K * 4 < kMaxBufBytes && (int64_t)Cout * K * 4 < kMaxBufBytes,
-              "operands larger than 2 GiB");
-  PPS_ENFORCE(aligned16(x) && aligned16(w), "x/w must be 16-byte aligned");
-  GemmParams p{};
-  p.splitk = splitk;
-  p.a = x; p.a_bstride = (int64_t)M * K; p.H = 1; p.W = M; p.Cin = K / splitk; p.lda = K;
-  p.a_bytes = (uint32_t)((int64_t)M * K * 4);
-  p.KH = p.KW = 1; p.stride = 1; p.dil = 1; p.Ho = 1; p.Wo = M; p.M = M;
-  p.ldb = K; p.kb_valid = K / splitk; p.Ncol = Cout;
-  p.Kloop = K / splitk;
-  p.out = part; p.ldo = (int64_t)B * Cout; p.out_bstride = Cout;
-  p.out_sstride = (int64_t)M * B * Cout; p.tile = tile;
-  if (x3) {
-    PPS_ENFORCE((int64_t)Cout * K * 6 < kMaxBufBytes, "weights larger than 2 GiB");
-    p.b3 = static_cast<const uint16_t*>(w); p.b_plane = (int64_t)Cout * K;
-    p.b_bstride = 3 * p.b_plane; p.b_bytes = (uint32_t)(p.b_plane * 2);
-    return launch_gemm_x3(p, EPI_CONV | EPI_F_RAW, B, as_stream(stream));
-  }
-  p.b = static_cast<const float*>(w); p.b_bstride = (int64_t)Cout * K;
-  p.b_bytes = (uint32_t)((int64_t)Cout * K * 4);
-  return launch_gemm(p, EPI_CONV | EPI_F_RAW, B, as_stream(stream));
 }
 
 int pps_gemm_splitk_batched(const float* x, int M, int K, const float* w, int Cout, int B,

@@ -283,18 +283,19 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
       set_error("f16x2 planes out: f32 activations, no split-K, Cin % 32 == 0");
       return PPS_ERR_INVALID_ARG;
     }
-    const int t = (p.tile < GEMM_TILE_P16_FIRST || p.tile == GEMM_TILE_WS ||
-                   p.tile >= GEMM_TILE_C16_FIRST) ? GEMM_TILE_P16_FIRST : p.tile;
-    return launch_gemm_x3p(p, epi, batch, stream, t - GEMM_TILE_P_FIRST);
+    const int t = tile_pipelined_x3(p.tile) && tile_kind(p.tile) == TileKind::P16
+                      ? p.tile
+                      : GEMM_TILE_P16_FIRST;
+    return launch_gemm_x3p(p, epi, batch, stream, t);
   }
   if ((p.tiled & 2) && !(epi & EPI_F_H2) &&
-      (p.tile == GEMM_TILE_WS || p.tile < GEMM_TILE_P_FIRST ||
+      (tile_kind(p.tile) == TileKind::WS || !tile_lands_pipelined(p.tile) ||
        (p.splitk > 1 && !p.ksplit_conv))) {
     set_error("chunk-tiled weights run on the pipelined / patch tiles only");
     return PPS_ERR_INVALID_ARG;
   }
-  if ((epi & EPI_F_FIX) && (!p.ksplit_conv || !p.fix_cnt || !p.part || p.tile < GEMM_TILE_P_FIRST ||
-                           p.tile == GEMM_TILE_WS || p.tile >= GEMM_TILE_C16_FIRST)) {
+  if ((epi & EPI_F_FIX) &&
+      (!p.ksplit_conv || !p.fix_cnt || !p.part || !tile_pipelined_x3(p.tile))) {
     set_error("one-launch conv split-K needs a pipelined tile, partials and counters");
     return PPS_ERR_INVALID_ARG;
   }
@@ -305,17 +306,14 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
     if (p.tile >= GEMM_TILE_C16_FIRST && x3c_eligible(p, epi, batch, p.tile))
       return launch_gemm_x3c(p, epi, stream, p.tile);
     if (p.tile == GEMM_TILE_WS && ws_eligible(p, epi, batch)) return launch_gemm_ws(p, epi, stream);
-    const int t = (p.tile == 0 || p.tile == GEMM_TILE_WS ||
-                   (p.tile >= GEMM_TILE_C16_FIRST && p.tile != GEMM_TILE_P16_192x128W41))
-                      ? GEMM_TILE_P16_FIRST
-                      : p.tile;
-    if (t < GEMM_TILE_P16_FIRST || t == GEMM_TILE_WS || batch != 1 || p.splitk != 1 ||
+    const int t = (p.tile == 0 || tile_falls_to_38(p.tile)) ? GEMM_TILE_P16_FIRST : p.tile;
+    if (tile_kind(t) != TileKind::P16 || batch != 1 || p.splitk != 1 ||
         !x3p_eligible(p, epi)) {
       set_error("f16x2 conv: a 16x16x32 pipelined or patch tile (38..53, 55..60), no split-K, "
                 "Cin % 32 == 0");
       return PPS_ERR_INVALID_ARG;
     }
-    return launch_gemm_x3p(p, epi, batch, stream, t - GEMM_TILE_P_FIRST);
+    return launch_gemm_x3p(p, epi, batch, stream, t);
   }
   if (p.tile == GEMM_TILE_WS) {
     // the weight-stationary kernel where it applies, else the 128x128
@@ -332,7 +330,7 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
     q.tile = GEMM_TILE_P16_FIRST;
     return launch_gemm_x3(q, epi_in, batch, stream);
   }
-  if (p.ksplit_conv && (p.tile < GEMM_TILE_P_FIRST || !x3p_eligible(p, epi))) {
+  if (p.ksplit_conv && (!tile_lands_pipelined(p.tile) || !x3p_eligible(p, epi))) {
     set_error("conv split-K runs on the pipelined tiles only (tile >= " +
               std::to_string((int)GEMM_TILE_P_FIRST) + ", Cin % 32 == 0)");
     return PPS_ERR_INVALID_ARG;
@@ -342,13 +340,12 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
     // lcm(BM, BN) super-blocks, gemm_x3p.hip); tile 0 = tile 43 (128 x 256,
     // the distance matrix's winner)
     const int t = p.tile ? p.tile : GEMM_TILE_P16_FIRST + 5;
-    if (!(epi & EPI_DIST) || p.M != p.Ncol || !x3p_eligible(p, epi) || t < GEMM_TILE_P_FIRST ||
-        t >= GEMM_TILE_C16_FIRST || t == GEMM_TILE_WS) {
+    if (!(epi & EPI_DIST) || p.M != p.Ncol || !x3p_eligible(p, epi) || !tile_pipelined_x3(t)) {
       set_error("symmetric distance: needs EPI_DIST, M == Ncol and a pipelined tile "
                 "(29..53 or 55)");
       return PPS_ERR_INVALID_ARG;
     }
-    return launch_gemm_x3p(p, epi, batch, stream, t - GEMM_TILE_P_FIRST);
+    return launch_gemm_x3p(p, epi, batch, stream, t);
   }
   if (p.a3 || (epi & EPI_F_PLANES)) {
     // bf16-plane activations exist only in the pipelined family
@@ -356,9 +353,10 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
       set_error("bf16-plane activations: shape/alignment not eligible for the pipelined GEMM");
       return PPS_ERR_INVALID_ARG;
     }
-    const int v = p.tile >= GEMM_TILE_P_FIRST ? p.tile - GEMM_TILE_P_FIRST
-                                              : (p.M % 192 == 0 ? 1 : 0);
-    return launch_gemm_x3p(p, epi, batch, stream, v);
+    const int t = tile_lands_pipelined(p.tile)
+                      ? p.tile
+                      : (p.M % 192 == 0 ? GEMM_TILE_P_FIRST + 1 : GEMM_TILE_P_FIRST);
+    return launch_gemm_x3p(p, epi, batch, stream, t);
   }
   // default for the distance matrix: the pipelined 256x128 tile on 16x16x32
   // blocks (the Market / Duke / 1M-shard autotune winner, scripts/dist_probe.py)
@@ -368,7 +366,7 @@ int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream) 
   if (tile >= GEMM_TILE_P_FIRST) {
     // LDS-DMA pipelined family (gemm_x3p.hip); shapes it cannot stage
     // (Cin % 32 != 0, unaligned rows) take the heuristic register-staged tile
-    if (x3p_eligible(p, epi)) return launch_gemm_x3p(p, epi, batch, stream, tile - GEMM_TILE_P_FIRST);
+    if (x3p_eligible(p, epi)) return launch_gemm_x3p(p, epi, batch, stream, tile);
     tile = pick_tile(p, batch);
   }
   const bool narrow_ok = p.Cin >= 32 || (p.Cin & (p.Cin - 1)) == 0;

@@ -22,6 +22,8 @@
 // (channel chunk, tap) order -- a different K order from tiles 38-55, so
 // these tiles agree bit for bit with each other, not with them (same
 // f32-level error, tests/test_gpu_x3.py).
+#include <utility>
+
 #include "gemm_x3p_common.hpp"
 
 #ifndef X3P_PRIO
@@ -349,34 +351,13 @@ static int launch_c(const GemmParams& p, int epi, hipStream_t stream) {
   return PPS_OK;
 }
 
-// Rows / columns / patch pixels of tiles 56-59.
-static void x3c_shape(int tile, int& bm, int& bn, int& pmax) {
-  switch (tile) {
-    case GEMM_TILE_C16_192x128: bm = 192; bn = 128; pmax = 272; return;
-    case GEMM_TILE_C16_192x64: bm = 192; bn = 64; pmax = 272; return;
-    case GEMM_TILE_C16_96x128: bm = 96; bn = 128; pmax = 144; return;
-    case GEMM_TILE_C16_192x64W42: bm = 192; bn = 64; pmax = 272; return;
-    default: bm = bn = pmax = 0; return;
-  }
-}
-
-int x3c_tile_rows(int tile) {
-  int bm, bn, pm;
-  x3c_shape(tile, bm, bn, pm);
-  return bm;
-}
-int x3c_tile_cols(int tile) {
-  int bm, bn, pm;
-  x3c_shape(tile, bm, bn, pm);
-  return bn;
-}
-
 // A stride-1 3x3 "same" conv whose tiles are whole output rows of one image
 // and whose patch fits; no fused shortcut, split-K or batching.
 bool x3c_eligible(const GemmParams& p, int epi, int batch, int tile) {
-  int bm, bn, pmax;
-  x3c_shape(tile, bm, bn, pmax);
-  if (!bm || batch != 1 || p.splitk > 1 || p.ksplit_conv || p.a2 || p.sym) return false;
+  const int row = x3c_tile_index(tile);
+  if (row < 0) return false;
+  const int bm = kX3cTiles[row].BM, pmax = kX3cTiles[row].PMAX;
+  if (batch != 1 || p.splitk > 1 || p.ksplit_conv || p.a2 || p.sym) return false;
   constexpr int C = EPI_CONV, RL = EPI_F_RELU, RS = EPI_F_RES, PL = EPI_F_PLANES;
   if (epi != C && epi != (C | RL) && epi != (C | RS) && epi != (C | RS | RL) && epi != (C | PL) &&
       epi != (C | RL | PL) && epi != (C | RL | EPI_F_H2))
@@ -389,29 +370,29 @@ bool x3c_eligible(const GemmParams& p, int epi, int batch, int tile) {
   return x3p_eligible(p, epi);
 }
 
+// The launch of row I of the patch tile table (gemm_tiles.hpp).
+template <int I>
+static int launch_row_c(const GemmParams& p, int epi, hipStream_t stream) {
+  constexpr X3cTile t = kX3cTiles[I];
+  return p.a3 ? launch_c<t.BM, t.BN, t.WM, t.WN, t.NSP, true, t.PMAX>(p, epi, stream)
+              : launch_c<t.BM, t.BN, t.WM, t.WN, t.NSF, false, t.PMAX>(p, epi, stream);
+}
+
+template <int... I>
+static int launch_rows_c(int row, const GemmParams& p, int epi, hipStream_t stream,
+                         std::integer_sequence<int, I...>) {
+  int rc = PPS_ERR_INVALID_ARG;
+  (void)((row == I && ((rc = launch_row_c<I>(p, epi, stream)), true)) || ...);
+  return rc;
+}
+
 int launch_gemm_x3c(const GemmParams& p, int epi, hipStream_t stream, int tile) {
-  const bool a3 = p.a3 != nullptr;
-  switch (tile) {
-    case GEMM_TILE_C16_192x128:
-      // 4 x 2 waves (48 x 64 each); weights in three stages (two with plane
-      // activations: 104 KB of patches)
-      return a3 ? launch_c<192, 128, 4, 2, 2, true, 272>(p, epi, stream)
-                : launch_c<192, 128, 4, 2, 3, false, 272>(p, epi, stream);
-    case GEMM_TILE_C16_192x64:
-      return a3 ? launch_c<192, 64, 4, 1, 4, true, 272>(p, epi, stream)
-                : launch_c<192, 64, 4, 1, 4, false, 272>(p, epi, stream);
-    case GEMM_TILE_C16_96x128:
-      return a3 ? launch_c<96, 128, 2, 4, 4, true, 144>(p, epi, stream)
-                : launch_c<96, 128, 2, 4, 4, false, 144>(p, epi, stream);
-    case GEMM_TILE_C16_192x64W42:
-      // 8 waves as 4 x 2 (48 x 32 each): half the weight bytes per tile of
-      // tile 57's neighbours at 256+ tiles for N = 256 (res4) / 128 (res3)
-      return a3 ? launch_c<192, 64, 4, 2, 4, true, 272>(p, epi, stream)
-                : launch_c<192, 64, 4, 2, 4, false, 272>(p, epi, stream);
-    default:
-      set_error("unknown patch-staged tile " + std::to_string(tile));
-      return PPS_ERR_INVALID_ARG;
+  const int row = x3c_tile_index(tile);
+  if (row < 0) {
+    set_error("unknown patch-staged tile " + std::to_string(tile));
+    return PPS_ERR_INVALID_ARG;
   }
+  return launch_rows_c(row, p, epi, stream, std::make_integer_sequence<int, kNumX3cTiles>());
 }
 
 }  // namespace pps

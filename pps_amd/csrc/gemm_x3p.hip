@@ -26,6 +26,8 @@
 // group); conv split-K (slices starting mid-im2col, raw partials); for the
 // distance epilogue a grouped tile order (GM query panels sweep the gallery
 // together) and the symmetric self-distance (upper-triangle tiles + mirror).
+#include <utility>
+
 #include "gemm_x3p_common.hpp"
 
 namespace pps {
@@ -644,63 +646,51 @@ static void launch_one_p(const GemmParams& p, int batch, hipStream_t stream) {
                      tiles_n);
 }
 
-// f16x2 arithmetic: f32 activations, chunk-tiled two-plane weights, the
-// conv epilogues of a ResNet bottleneck (16x16x32 tiles only)
-template <int BM, int BN, int WM, int WN, int NSF>
-static int launch_tile_h2(const GemmParams& p, int epi, int batch, hipStream_t stream) {
+// f16x2 arithmetic: f32 activations (or, A3, the f16x2 activation planes of
+// pps_split_f16x2_act / a producer's EPI_F_H2OUT), chunk-tiled two-plane
+// weights, the conv epilogues of a ResNet bottleneck (16x16x32 tiles only)
+template <int BM, int BN, int WM, int WN, int NSF, bool A3>
+static int launch_tile_h2a(const GemmParams& p, int epi, int batch, hipStream_t stream) {
   constexpr int C = EPI_CONV, RL = EPI_F_RELU, RS = EPI_F_RES, H = EPI_F_H2, S = 16;
-  if (!(p.tiled & 2) || !p.rs_b || !p.amax_a || ((epi & EPI_F_DUAL) && (!p.amax_a2 || p.a3))) {
-    set_error("f16x2 conv: activations (f32, or f16x2 planes) with their max, chunk-tiled "
-              "weights and scales; the fused shortcut reads f32");
-    return PPS_ERR_INVALID_ARG;
-  }
   constexpr int HO = EPI_F_H2OUT;
-  if (p.a3) {   // f16x2 activation planes (pps_split_f16x2_act or a producer's EPI_F_H2OUT)
-    switch (epi & ~H) {
-      case C | RL: launch_one_p<BM, BN, WM, WN, NSF, C | RL | H, true, S>(p, batch, stream); break;
-      case C | RL | HO:
-        launch_one_p<BM, BN, WM, WN, NSF, C | RL | HO | H, true, S>(p, batch, stream); break;
-      case C | RS | RL:
-        launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | H, true, S>(p, batch, stream); break;
-      case C | RS | RL | EPI_F_PPS:
-        if constexpr (BM == 192 && BN <= 256) {
-          launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | EPI_F_PPS | H, true, S>(p, batch, stream);
-          break;
-        } else {
-          set_error("part-power-set epilogue needs a 192-row tile with at most 256 columns");
-          return PPS_ERR_INVALID_ARG;
-        }
-      default:
-        set_error("f16x2 conv on activation planes: conv + BN + ReLU [+ residual | part "
-                  "pooling] only");
-        return PPS_ERR_INVALID_ARG;
-    }
-    PPS_CHECK_LAUNCH("gemm_x3p_kernel");
-    return PPS_OK;
-  }
   switch (epi & ~H) {
-    case C | RL: launch_one_p<BM, BN, WM, WN, NSF, C | RL | H, false, S>(p, batch, stream); break;
+    case C | RL: launch_one_p<BM, BN, WM, WN, NSF, C | RL | H, A3, S>(p, batch, stream); break;
     case C | RL | HO:
-      launch_one_p<BM, BN, WM, WN, NSF, C | RL | HO | H, false, S>(p, batch, stream); break;
+      launch_one_p<BM, BN, WM, WN, NSF, C | RL | HO | H, A3, S>(p, batch, stream); break;
     case C | RS | RL:
-      launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | H, false, S>(p, batch, stream); break;
-    case C | RL | EPI_F_DUAL:
-      launch_one_p<BM, BN, WM, WN, NSF, C | RL | EPI_F_DUAL | H, false, S>(p, batch, stream);
-      break;
+      launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | H, A3, S>(p, batch, stream); break;
     case C | RS | RL | EPI_F_PPS:
       if constexpr (BM == 192 && BN <= 256) {
-        launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | EPI_F_PPS | H, false, S>(p, batch, stream);
+        launch_one_p<BM, BN, WM, WN, NSF, C | RS | RL | EPI_F_PPS | H, A3, S>(p, batch, stream);
         break;
       } else {
         set_error("part-power-set epilogue needs a 192-row tile with at most 256 columns");
         return PPS_ERR_INVALID_ARG;
       }
+    case C | RL | EPI_F_DUAL:  // (the fused shortcut reads f32)
+      if constexpr (!A3) {
+        launch_one_p<BM, BN, WM, WN, NSF, C | RL | EPI_F_DUAL | H, A3, S>(p, batch, stream);
+        break;
+      }
+      [[fallthrough]];
     default:
-      set_error("f16x2 conv: conv + BN + ReLU [+ residual | shortcut | part pooling] only");
+      set_error(A3 ? "f16x2 conv on activation planes: conv + BN + ReLU [+ residual | part "
+                     "pooling] only"
+                   : "f16x2 conv: conv + BN + ReLU [+ residual | shortcut | part pooling] only");
       return PPS_ERR_INVALID_ARG;
   }
   PPS_CHECK_LAUNCH("gemm_x3p_kernel");
   return PPS_OK;
+}
+template <int BM, int BN, int WM, int WN, int NSF>
+static int launch_tile_h2(const GemmParams& p, int epi, int batch, hipStream_t stream) {
+  if (!(p.tiled & 2) || !p.rs_b || !p.amax_a || ((epi & EPI_F_DUAL) && (!p.amax_a2 || p.a3))) {
+    set_error("f16x2 conv: activations (f32, or f16x2 planes) with their max, chunk-tiled "
+              "weights and scales; the fused shortcut reads f32");
+    return PPS_ERR_INVALID_ARG;
+  }
+  return p.a3 ? launch_tile_h2a<BM, BN, WM, WN, NSF, true>(p, epi, batch, stream)
+              : launch_tile_h2a<BM, BN, WM, WN, NSF, false>(p, epi, batch, stream);
 }
 
 // NSF / NSP: LDS stages with f32 / bf16-plane A operands (NSP = 0: the tile
@@ -843,131 +833,51 @@ bool x3p_eligible(const GemmParams& p, int epi) {
   return true;
 }
 
-// variants 0..8: 32x32x16 MFMA blocks (bit-identical to gemm_x3.hip);
-// 9..17: the same tiles on 16x16x32 MFMA blocks (bit-identical among
-// themselves, f32-level like the others).
-template <int S>
-static int launch_variant(const GemmParams& p, int epi, int batch, hipStream_t stream, int v) {
-  switch (v) {
-    // 4-wave tiles up to 80 KB of LDS take two stages: two workgroups per CU,
-    // so one's epilogue overlaps the other's loads (measured 10-30 % faster
-    // than three stages at one workgroup per CU on every layer shape,
-    // scripts/gemm_probe.py); 192x128 needs 96 KB for two stages anyway
-    case 0: return launch_tile_p<128, 128, 2, 2, 2, 2, S>(p, epi, batch, stream);
-    case 1: return launch_tile_p<192, 128, 2, 2, 3, 2, S>(p, epi, batch, stream);
-    case 2: return launch_tile_p<128, 64, 2, 2, 2, 2, S>(p, epi, batch, stream);
-    case 3: return launch_tile_p<192, 64, 2, 2, 2, 2, S>(p, epi, batch, stream);
-    case 4: return launch_tile_p<256, 128, 4, 2, 2, 2, S>(p, epi, batch, stream);
-    case 5: return launch_tile_p<128, 256, 2, 4, 2, 2, S>(p, epi, batch, stream);
-    case 6:
-      // 192x256 with plane A needs 168 KB for two stages, and on 16x16 blocks
-      // more than the 256 VGPRs of an 8-wave workgroup: 128x256 instead
-      if (p.a3 || S == 16) return launch_tile_p<128, 256, 2, 4, 2, 2, S>(p, epi, batch, stream);
-      if constexpr (S == 32) return launch_tile_p<192, 256, 2, 4, 2, 0, S>(p, epi, batch, stream);
-    // 8-wave versions of 128x128 / 192x128 (two waves per SIMD in one
-    // workgroup; 128x128 also two workgroups per CU): res3/res4 3x3 and
-    // res4 2c run 6-10 % faster on them
-    case 7: return launch_tile_p<128, 128, 4, 2, 2, 2, S, S == 16>(p, epi, batch, stream);
-    case 8:  // plane A: 12 pieces of 16 rows over 8 waves (uneven, two stages)
-      return launch_tile_p<192, 128, 2, 4, 2, 2, S>(p, epi, batch, stream);
-    default:
-      set_error("unknown pipelined GEMM variant " + std::to_string(v));
-      return PPS_ERR_INVALID_ARG;
-  }
-}
-
-// Rows (BM) of the tile a pipelined id launches (as launch_variant /
-// launch_gemm_x3p map it), 0 for a non-pipelined id.
-int x3p_tile_rows(int tile, bool a3) {
-  if (tile == GEMM_TILE_P16_64x128W24S4) return 64;
-  if (tile == GEMM_TILE_P16_192x128W41) return 192;
-  if (tile < GEMM_TILE_P_FIRST || tile >= GEMM_TILE_WS) return 0;
-  if (tile == GEMM_TILE_P16_192x128W42 || tile == GEMM_TILE_P16_192x64W41 ||
-      tile == GEMM_TILE_P16_192x128W42S3 || tile == GEMM_TILE_P16_192x128W41)
-    return 192;
-  if (tile == GEMM_TILE_P16_128x128W42S3) return 128;
-  if (tile == GEMM_TILE_P16_96x128W22 || tile == GEMM_TILE_P16_96x128W24 ||
-      tile == GEMM_TILE_P16_96x128W24S3)
-    return 96;
-  constexpr int NV = GEMM_TILE_P16_FIRST - GEMM_TILE_P_FIRST;
-  const int v = (tile - GEMM_TILE_P_FIRST) % NV;
-  const bool s16 = tile >= GEMM_TILE_P16_FIRST;
-  switch (v) {
-    case 0: case 2: case 5: case 7: return 128;
-    case 1: case 3: return 192;
-    case 4: return 256;
-    case 6: return (a3 || s16) ? 128 : 192;
-    case 8: return 192;
-    default: return 0;
-  }
-}
-
-// Columns (BN) of that tile.
-int x3p_tile_cols(int tile, bool a3) {
-  if (tile == GEMM_TILE_P16_64x128W24S4 || tile == GEMM_TILE_P16_192x128W41) return 128;
-  if (tile < GEMM_TILE_P_FIRST || tile >= GEMM_TILE_WS) return 0;
-  if (tile == GEMM_TILE_P16_192x128W42 || tile == GEMM_TILE_P16_96x128W22 ||
-      tile == GEMM_TILE_P16_96x128W24 || tile == GEMM_TILE_P16_128x128W42S3 ||
-      tile == GEMM_TILE_P16_192x128W42S3 || tile == GEMM_TILE_P16_96x128W24S3)
-    return 128;
-  if (tile == GEMM_TILE_P16_192x64W41) return 64;
-  constexpr int NV = GEMM_TILE_P16_FIRST - GEMM_TILE_P_FIRST;
-  const int v = (tile - GEMM_TILE_P_FIRST) % NV;
-  (void)a3;
-  switch (v) {
-    case 2: case 3: return 64;
-    case 5: case 6: return 256;
-    default: return 128;
-  }
-}
-
-int launch_gemm_x3p(const GemmParams& p, int epi, int batch, hipStream_t stream, int variant) {
-  constexpr int NV = GEMM_TILE_P16_FIRST - GEMM_TILE_P_FIRST;  // variants per block size
-  // plane A on the 192-row 8-wave and 96-row tiles: 12 / 6 pieces of 16 rows
-  // spread unevenly over the waves (two stages)
-  if (variant == GEMM_TILE_P16_192x128W42 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<192, 128, 4, 2, 2, 2, 16, true>(p, epi, batch, stream);
-  if (variant == GEMM_TILE_P16_192x64W41 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<192, 64, 4, 1, 2, 2, 16, true>(p, epi, batch, stream);
-  if (variant == GEMM_TILE_P16_96x128W22 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<96, 128, 2, 2, 2, 2, 16, true>(p, epi, batch, stream);
-  // 96x128 with 8 waves as 2 x 4 (48 x 32 per wave): 256 tiles for
-  // M = 12,288 x N = 256 at two waves per SIMD
-  if (variant == GEMM_TILE_P16_96x128W24 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<96, 128, 2, 4, 2, 2, 16, true>(p, epi, batch, stream);
-  // three LDS stages (two chunks in flight behind the one being consumed) on
-  // the 8-wave 128x128 / 192x128 tiles, for long-K GEMMs whose operands come
-  // from the Infinity Cache rather than L2 (distance matrix, res5);
-  // 192-row plane A keeps two stages (uneven pieces)
 #ifndef X3P_DEEP
 #define X3P_DEEP 0  // probes: 1 = four LDS stages for f32 A on tiles 51 / 53
 #endif
-  if (variant == GEMM_TILE_P16_128x128W42S3 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<128, 128, 4, 2, X3P_DEEP ? 4 : 3, 3, 16>(p, epi, batch, stream);
 #ifndef X3P_DEEP52
 #define X3P_DEEP52 0  // probes: 1 = four LDS stages (160 KB) on tile 52
 #endif
-  if (variant == GEMM_TILE_P16_192x128W42S3 - GEMM_TILE_P_FIRST) {
-    if (X3P_DEEP52 && (epi & EPI_F_H2)) return launch_tile_h2<192, 128, 4, 2, 4>(p, epi, batch, stream);
-    return launch_tile_p<192, 128, 4, 2, 3, 2, 16>(p, epi, batch, stream);
+
+// The launch of row I of the pipelined tile table (gemm_tiles.hpp).
+template <int I>
+static int launch_row(const GemmParams& p, int epi, int batch, hipStream_t stream) {
+  constexpr X3pTile t = kX3pTiles[I];
+  if constexpr (t.x3_id != 0) {  // f16x2 only (launch_gemm_x3p sends bf16x3 to row x3_id)
+    return launch_tile_h2<t.BM, t.BN, t.WM, t.WN, t.NSF>(p, epi, batch, stream);
+  } else {
+    constexpr bool deep = X3P_DEEP && (t.id == GEMM_TILE_P16_128x128W42S3 ||
+                                       t.id == GEMM_TILE_P16_96x128W24S3);
+    if constexpr (t.id == GEMM_TILE_P16_192x128W42S3) {  // (its kernels are built either way)
+      if (X3P_DEEP52 && (epi & EPI_F_H2))
+        return launch_tile_h2<t.BM, t.BN, t.WM, t.WN, 4>(p, epi, batch, stream);
+    }
+    return launch_tile_p<t.BM, t.BN, t.WM, t.WN, deep ? 4 : t.NSF, t.NSP, t.S, t.FX>(p, epi, batch,
+                                                                                    stream);
   }
-  // 96x128 as 2 x 4 waves with three stages (uneven pieces, per-wave waits)
-  if (variant == GEMM_TILE_P16_96x128W24S3 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<96, 128, 2, 4, X3P_DEEP ? 4 : 3, 3, 16>(p, epi, batch, stream);
-  // 64x128, 8 waves as 2 x 4, four stages (three chunks in flight): the
-  // 64-row split-K head GEMMs, whose 8-chunk slices are all pipeline fill
-  if (variant == GEMM_TILE_P16_64x128W24S4 - GEMM_TILE_P_FIRST)
-    return launch_tile_p<64, 128, 2, 4, 4, 4, 16>(p, epi, batch, stream);
-  // f16x2 only: 192x128 as 4 x 1 waves (48 x 128 per wave): each activation
-  // fragment split once feeds eight 16x16 column blocks (the split is the
-  // f16x2 kernels' VALU cost; 4 x 2 waves split every fragment twice and
-  // feed four).  bf16x3 launches of this id run tile 47 (same rounding group).
-  if (variant == GEMM_TILE_P16_192x128W41 - GEMM_TILE_P_FIRST) {
-    if (epi & EPI_F_H2) return launch_tile_h2<192, 128, 4, 1, 2>(p, epi, batch, stream);
-    return launch_tile_p<192, 128, 4, 2, 2, 2, 16, true>(p, epi, batch, stream);
+}
+
+template <int... I>
+static int launch_rows(int row, const GemmParams& p, int epi, int batch, hipStream_t stream,
+                       std::integer_sequence<int, I...>) {
+  int rc = PPS_ERR_INVALID_ARG;
+  (void)((row == I && ((rc = launch_row<I>(p, epi, batch, stream)), true)) || ...);
+  return rc;
+}
+
+int launch_gemm_x3p(const GemmParams& p, int epi, int batch, hipStream_t stream, int tile) {
+  int row = x3p_shape_index(tile, p.a3 != nullptr);
+  // an f16x2-only tile's bf16x3 launches run its twin of the same rounding group
+  if (row >= 0 && kX3pTiles[row].x3_id && !(epi & EPI_F_H2))
+    row = x3p_tile_index(kX3pTiles[row].x3_id);
+  if (row < 0) {
+    constexpr int NV = GEMM_TILE_P16_FIRST - GEMM_TILE_P_FIRST;  // ids per block size
+    const int v = tile - GEMM_TILE_P_FIRST;
+    set_error("unknown pipelined GEMM variant " + std::to_string(v >= NV ? v - NV : v));
+    return PPS_ERR_INVALID_ARG;
   }
-  if (variant >= NV) return launch_variant<16>(p, epi, batch, stream, variant - NV);
-  return launch_variant<32>(p, epi, batch, stream, variant);
+  return launch_rows(row, p, epi, batch, stream, std::make_integer_sequence<int, kNumX3pTiles>());
 }
 
 }  // namespace pps

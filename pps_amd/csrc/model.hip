@@ -636,14 +636,13 @@ std::map<std::string, Shape> infer_shapes(const PpsModel& m, int N) {
   return s;
 }
 
-std::vector<int> pps_tiles(const PpsModel& m, const Layer& L, const Shape& conv_shape) {
+std::vector<int> pps_tiles(const Layer& L, const Shape& conv_shape) {
   std::vector<int> out;
   const int rows = (int)(conv_shape.d[1] * conv_shape.d[2]);
   for (int t = GEMM_TILE_P_FIRST; t < GEMM_NUM_TILES; ++t) {
     const int r = x3p_tile_rows(t, L.planes_in), c = x3p_tile_cols(t, L.planes_in);
     if (r == rows && c > 0 && c <= kPpsFuseMaxCols) out.push_back(t);
   }
-  (void)m;
   return out;
 }
 
@@ -664,7 +663,6 @@ size_t part_need(const PpsModel& m, const std::map<std::string, Shape>& shapes) 
   return need;
 }
 
-// tiles built with the one-launch split-K epilogue (gemm_x3p.hip FX)
 // A branch2c -> next branch2a pair the seam kernel covers (structure only;
 // seam_ok adds the table's conditions)
 bool seam_pair(const PpsModel& m, size_t i) {
@@ -709,8 +707,8 @@ bool h2_tile_ok(const Layer& L, int tile) {
   if (base == 0) return true;
   if (base == GEMM_TILE_WS)  // the weight-stationary 1x1 (f32 input, K = 64 / 128 / 256)
     return ws_h2_layer(L) && !(tile & (PPS_TILE_H2P | PPS_TILE_H2E));
-  if (base < GEMM_TILE_P16_FIRST || base >= GEMM_NUM_TILES) return false;
-  return L.op == Op::Conv || base < GEMM_TILE_C16_FIRST || base == GEMM_TILE_P16_192x128W41;
+  if (!tile_rounds_16(base)) return false;
+  return L.op == Op::Conv || tile_kind(base) != TileKind::Patch;  // patch tiles: plain convs
 }
 
 // The producer whose f16x2-planes output a PPS_TILE_H2E layer C reads
@@ -728,11 +726,8 @@ int h2e_producer(const PpsModel& m, const Layer& C) {
   return -1;
 }
 
-bool fix_tile(int tile) {
-  const int t = tile & 0xff;
-  return t == GEMM_TILE_P16_FIRST + 7 ||
-         (t >= GEMM_TILE_P16_192x128W42 && t <= GEMM_TILE_P16_96x128W24);
-}
+// tiles built with the one-launch split-K epilogue (the tile table's FX)
+bool fix_tile(int tile) { return x3p_tile_fix(tile & 0xff); }
 
 // tile counters for the one-launch split-K: an upper bound on the output
 // tiles of any split conv (the smallest FIX tile is 96 x 128 / 192 x 64)
@@ -805,7 +800,7 @@ Workspace& workspace(const PpsModel& m, int N, hipStream_t st, bool allow_alloc)
   w.shapes = infer_shapes(m, N);
   bool need_conv_out = false;
   for (const auto& L : m.layers)
-    if (L.op == Op::ConvPps && pps_tiles(m, L, w.shapes.at(L.conv_output)).empty())
+    if (L.op == Op::ConvPps && pps_tiles(L, w.shapes.at(L.conv_output)).empty())
       need_conv_out = true;
   for (const auto& kv : w.shapes) {
     if (kv.first == "data") continue;
@@ -957,64 +952,58 @@ void run_layer(const PpsModel& m, const Layer& L, Workspace& w, const float* x, 
       if (h2e_c)
         PPS_MCHECK(amo && slotp(L.input), "layer '" + L.name + "': f16x2 planes out needs the "
                                           "input's and the output's activation slots");
-      if (h2) {
-        int64_t xpl = 0;
-        const uint16_t* xp = (h2p || h2e) ? h2_planes(a, &xpl) : nullptr;
-        rc_check(conv_impl(xp ? nullptr : a.f, n, H, W, L.cin_eff, ldx, L.w2->as<uint16_t>(), 1,
-                           L.cout, L.kpad, L.k, L.k, L.stride, L.pad, L.dil, sc, sh, res, L.relu,
-                           yh2 ? nullptr : fbuf(L.output), Ho, Wo, L.cout, tile, st, xp, xpl,
-                           nullptr, 0, 1, nullptr, nullptr, 0, amo, L.wrs->as<float>(),
-                           slotp(L.input), yh2, yh2_plane, slotp(L.input), L.h2o_bw, L.h2o_bb));
-      } else if (yh2) {   // bf16x3 arithmetic, f16x2 planes out
-        rc_check(conv_impl(a.f, n, H, W, L.cin_eff, ldx, w3, 1, L.cout, L.kpad, L.k, L.k,
-                           L.stride, L.pad, L.dil, sc, sh, res, L.relu, nullptr, Ho, Wo, L.cout,
-                           tile, st, nullptr, 0, nullptr, 0, 1, nullptr, nullptr, 0, amo, nullptr,
-                           nullptr, yh2, yh2_plane, slotp(L.input), L.h2o_bw, L.h2o_bb));
-      } else if (m.x3 && (L.planes_in || L.planes_out || sk > 1)) {
-        const int t = tile >= GEMM_TILE_P_FIRST ? tile : 0;
-        float* yf = L.planes_out ? nullptr : fbuf(L.output);
-        uint16_t* y3 = L.planes_out ? w.bufs.at(L.output)->as<uint16_t>() : nullptr;
-        const int64_t ypl = L.planes_out ? ys.numel() : 0;
-        if (fused_sk)
-          rc_check(conv_impl(a.f, n, H, W, L.cin_eff, ldx, w3, 1, L.cout, L.kpad, L.k, L.k,
-                             L.stride, L.pad, L.dil, sc, sh, res, L.relu, yf, Ho, Wo, L.cout, t,
-                             st, a.pl, a.plane, y3, ypl, sk, w.part->as<float>(),
-                             w.cnt->as<int>(), (int64_t)w.cnt_ints, amo, nullptr, nullptr));
-        else
-          rc_check(conv_impl(a.f, n, H, W, L.cin_eff, ldx, w3, 1, L.cout, L.kpad, L.k, L.k,
-                             L.stride, L.pad, L.dil, sc, sh, res, L.relu, yf, Ho, Wo, L.cout, t,
-                             st, a.pl, a.plane, y3, ypl, sk, sk > 1 ? w.part->as<float>() : nullptr,
-                             nullptr, 0, amo, nullptr, nullptr));
-      } else if (m.x3) {
-        rc_check(conv_impl(a.f, n, H, W, L.cin_eff, ldx, w3, 1, L.cout, L.kpad, L.k, L.k,
-                           L.stride, L.pad, L.dil, sc, sh, res, L.relu, fbuf(L.output), Ho, Wo,
-                           L.cout, tile, st, nullptr, 0, nullptr, 0, 1, nullptr, nullptr, 0, amo,
-                           nullptr, nullptr));
-      } else {
-        rc_check(pps_conv2d_bn_act(a.f, n, H, W, L.cin_eff, ldx, wf, L.cout, L.kpad, L.k, L.k,
-                                   L.stride, L.pad, L.dil, sc, sh, res, L.relu, fbuf(L.output),
-                                   Ho, Wo, L.cout, tile, st));
+      ConvArgs c;
+      c.x = a.f; c.N = n; c.H = H; c.W = W; c.Cin = L.cin_eff; c.ldx = ldx;
+      c.w = m.x3 ? (const void*)w3 : (const void*)wf; c.x3 = m.x3;
+      c.Cout = L.cout; c.Kpad = L.kpad; c.KH = c.KW = L.k;
+      c.stride = L.stride; c.pad = L.pad; c.dil = L.dil;
+      c.scale = sc; c.shift = sh; c.residual = res; c.relu = L.relu;
+      c.y = fbuf(L.output); c.Ho = Ho; c.Wo = Wo; c.ldy = L.cout;
+      c.tile = tile; c.stream = st;
+      if (m.x3) c.amax_out = amo;  // (the f32 path is pps_conv2d_bn_act: no max reported)
+      if (yh2) {  // f16x2 planes out, from either arithmetic
+        c.y = nullptr; c.y_h2 = yh2; c.y_h2_plane = yh2_plane;
+        c.h2o_in = slotp(L.input); c.h2o_bw = L.h2o_bw; c.h2o_bb = L.h2o_bb;
       }
+      if (h2) {
+        c.w = L.w2->as<uint16_t>(); c.w_rs = L.wrs->as<float>(); c.amax_in = slotp(L.input);
+        if (h2p || h2e) {
+          c.x_pl = h2_planes(a, &c.x_plane);
+          if (c.x_pl) c.x = nullptr;
+        }
+      } else if (m.x3 && !yh2 && (L.planes_in || L.planes_out || sk > 1)) {
+        c.tile = tile_lands_pipelined(tile) ? tile : 0;
+        c.x_pl = a.pl; c.x_plane = a.plane;
+        if (L.planes_out) {
+          c.y = nullptr; c.y_pl = w.bufs.at(L.output)->as<uint16_t>(); c.y_plane = ys.numel();
+        }
+        c.splitk = sk;
+        if (sk > 1) c.part = w.part->as<float>();
+        if (fused_sk) { c.fix_cnt = w.cnt->as<int>(); c.n_cnt = (int64_t)w.cnt_ints; }
+      }
+      rc_check(conv_impl(c));
       return;
     }
     case Op::ConvDual: {
       const Act a = act(L.input, false), b = act(L.input2, false);
       const Shape ys = w.shapes.at(L.output);
       const int C2 = (int)b.s.d[3];
-      if (m.x3)
-        rc_check(dual_impl(a.f, (int)a.s.d[0], (int)a.s.d[1], (int)a.s.d[2], L.cin_eff,
-                           (int)a.s.d[3], L.k, L.k, L.stride, L.pad, b.f, (int)b.s.d[1],
-                           (int)b.s.d[2], C2, C2, L.stride2,
-                           h2 ? L.w2->as<uint16_t>() : w3, 1, L.cout, L.kpad, C2, sh, L.relu,
-                           fbuf(L.output), (int)ys.d[1], (int)ys.d[2], L.cout, tile, st,
-                           slotp(L.output), h2 ? L.wrs->as<float>() : nullptr,
-                           h2 ? slotp(L.input) : nullptr, h2 ? slotp(L.input2) : nullptr));
-      else
-        rc_check(pps_conv2d_dual_bn_act(a.f, (int)a.s.d[0], (int)a.s.d[1], (int)a.s.d[2],
-                                        L.cin_eff, (int)a.s.d[3], L.k, L.k, L.stride, L.pad, b.f,
-                                        (int)b.s.d[1], (int)b.s.d[2], C2, C2, L.stride2, wf,
-                                        L.cout, L.kpad, C2, sh, L.relu, fbuf(L.output),
-                                        (int)ys.d[1], (int)ys.d[2], L.cout, tile, st));
+      DualArgs c;
+      c.x = a.f; c.N = (int)a.s.d[0]; c.H = (int)a.s.d[1]; c.W = (int)a.s.d[2];
+      c.Cin = L.cin_eff; c.ldx = (int)a.s.d[3];
+      c.KH = c.KW = L.k; c.stride = L.stride; c.pad = L.pad;
+      c.x2 = b.f; c.H2 = (int)b.s.d[1]; c.W2 = (int)b.s.d[2]; c.Cin2 = c.ldx2 = C2;
+      c.stride2 = L.stride2;
+      c.w = m.x3 ? (const void*)w3 : (const void*)wf; c.x3 = m.x3;
+      c.Cout = L.cout; c.Kpad = L.kpad; c.Kpad2 = C2; c.shift = sh; c.relu = L.relu;
+      c.y = fbuf(L.output); c.Ho = (int)ys.d[1]; c.Wo = (int)ys.d[2]; c.ldy = L.cout;
+      c.tile = tile; c.stream = st;
+      if (m.x3) c.amax_out = slotp(L.output);  // (the f32 path is pps_conv2d_dual_bn_act)
+      if (m.x3 && h2) {
+        c.w = L.w2->as<uint16_t>(); c.w_rs = L.wrs->as<float>();
+        c.amax_in = slotp(L.input); c.amax_in2 = slotp(L.input2);
+      }
+      rc_check(dual_impl(c));
       return;
     }
     case Op::MaxPool: {
@@ -1055,43 +1044,42 @@ void run_layer(const PpsModel& m, const Layer& L, Workspace& w, const float* x, 
       const Act a = act(L.input, L.planes_in);
       const Shape cs = w.shapes.at(L.conv_output);
       const float* res = fbuf(L.residual);
-      const std::vector<int> ok = pps_tiles(m, L, cs);
-      const int n = (int)a.s.d[0], H = (int)a.s.d[1], W = (int)a.s.d[2], ldx = (int)a.s.d[3];
+      const std::vector<int> ok = pps_tiles(L, cs);
+      ConvArgs c;
+      c.x = a.f; c.x_pl = a.pl; c.x_plane = a.plane;
+      c.N = (int)a.s.d[0]; c.H = (int)a.s.d[1]; c.W = (int)a.s.d[2]; c.ldx = (int)a.s.d[3];
+      c.Cin = L.cin_eff; c.w = w3; c.x3 = 1; c.Cout = L.cout; c.Kpad = L.kpad; c.KH = c.KW = L.k;
+      c.stride = L.stride; c.pad = L.pad; c.dil = L.dil;
+      c.scale = sc; c.shift = sh; c.residual = res; c.Ho = (int)cs.d[1]; c.Wo = (int)cs.d[2];
+      c.splits = L.split.data(); c.S = (int)L.split.size(); c.max_ave = L.max_ave;
+      c.pps_out = fbuf(L.output); c.stream = st;
       if (h2) {  // f16x2: the 192-row tiles on 16x16x32 blocks
         std::vector<int> ok16;
         for (int t : ok)
           if (t >= GEMM_TILE_P16_FIRST) ok16.push_back(t);
         PPS_MCHECK(!ok16.empty(), "layer '" + L.name + "': no f16x2 tile holds one image");
         const int tb = tile & ~PPS_TILE_COL_ORDER;
-        int t = std::find(ok16.begin(), ok16.end(), tb) != ok16.end() ? tb : ok16[0];
-        t |= tile & PPS_TILE_COL_ORDER;
-        int64_t xpl = 0;
-        const uint16_t* xp = (h2p || h2e) ? h2_planes(a, &xpl) : nullptr;
-        rc_check(conv_pps_impl(xp ? nullptr : a.f, xp, xpl, n, H, W, L.cin_eff, ldx,
-                               L.w2->as<uint16_t>(),
-                               L.cout, L.kpad, L.k, L.k, L.stride, L.pad, L.dil, sc, sh, res,
-                               nullptr, (int)cs.d[1], (int)cs.d[2], L.split.data(),
-                               (int)L.split.size(), L.max_ave, fbuf(L.output), t, st,
-                               L.wrs->as<float>(), slotp(L.input)));
+        c.tile = std::find(ok16.begin(), ok16.end(), tb) != ok16.end() ? tb : ok16[0];
+        c.tile |= tile & PPS_TILE_COL_ORDER;
+        if (h2p || h2e) {
+          c.x_pl = h2_planes(a, &c.x_plane);
+          c.x = nullptr;
+        }
+        c.w = L.w2->as<uint16_t>(); c.w_rs = L.wrs->as<float>(); c.amax_in = slotp(L.input);
       } else if (!ok.empty()) {
         const int tb = tile & ~(PPS_TILE_B_TILED | PPS_TILE_COL_ORDER);
-        int t = std::find(ok.begin(), ok.end(), tb) != ok.end() ? tb : ok[0];
-        t |= tile & PPS_TILE_COL_ORDER;
-        if (wtiled) t |= PPS_TILE_B_TILED;
-        rc_check(pps_conv2d_bn_act_pps_x3p(a.f, a.pl, a.plane, n, H, W, L.cin_eff, ldx, w3,
-                                           L.cout, L.kpad, L.k, L.k, L.stride, L.pad, L.dil, sc,
-                                           sh, res, nullptr, (int)cs.d[1], (int)cs.d[2],
-                                           L.split.data(), (int)L.split.size(), L.max_ave,
-                                           fbuf(L.output), t, st));
+        c.tile = std::find(ok.begin(), ok.end(), tb) != ok.end() ? tb : ok[0];
+        c.tile |= tile & PPS_TILE_COL_ORDER;
+        if (wtiled) c.tile |= PPS_TILE_B_TILED;
       } else {  // no tile holds exactly one image: conv, then the pooling kernel
-        float* y = fbuf(L.conv_output);
-        rc_check(pps_conv2d_bn_act_x3p(a.f, a.pl, a.plane, n, H, W, L.cin_eff, ldx, w3, L.cout,
-                                       L.kpad, L.k, L.k, L.stride, L.pad, L.dil, sc, sh, res, 1,
-                                       y, nullptr, 0, (int)cs.d[1], (int)cs.d[2], L.cout,
-                                       tile >= GEMM_TILE_P_FIRST ? tile | (wtiled ? PPS_TILE_B_TILED : 0) : 0, st));
-        rc_check(pps_part_power_set(y, n, (int)cs.d[1], (int)cs.d[2], L.cout, L.split.data(),
-                                    (int)L.split.size(), L.max_ave, fbuf(L.output), st));
+        c.relu = 1; c.y = fbuf(L.conv_output); c.ldy = L.cout;
+        c.tile = tile_lands_pipelined(tile) ? tile | (wtiled ? PPS_TILE_B_TILED : 0) : 0;
+        rc_check(conv_impl(c));
+        rc_check(pps_part_power_set(c.y, c.N, c.Ho, c.Wo, L.cout, L.split.data(), c.S, L.max_ave,
+                                    fbuf(L.output), st));
+        return;
       }
+      rc_check(conv_pps_impl(c));
       return;
     }
     case Op::Heads: {
@@ -1587,10 +1575,11 @@ int pps_model_set_tile(PpsModel* m, const char* layer, int tile) {
                std::string("PPS_TILE_SEAM: '") + layer +
                    "' is not a branch2c feeding a seam-capable branch2a (base tile 54)");
     PPS_MCHECK(!(tile & PPS_TILE_B_TILED) ||
-                   (L->wt && base >= GEMM_TILE_P_FIRST && base != GEMM_TILE_WS),
+                   (L->wt && tile_lands_pipelined(base) && tile_kind(base) != TileKind::WS),
                "PPS_TILE_B_TILED: x3 conv with Cin % 32 == 0 on a pipelined tile only");
     PPS_MCHECK(!(tile & PPS_TILE_COL_ORDER) ||
-                   (L->op != Op::Heads && base >= GEMM_TILE_P_FIRST && base != GEMM_TILE_WS),
+                   (L->op != Op::Heads && tile_lands_pipelined(base) &&
+                    tile_kind(base) != TileKind::WS),
                "PPS_TILE_COL_ORDER: conv layers on a pipelined tile only");
     L->tile = tile;
   });
@@ -1794,7 +1783,7 @@ int pps_model_autotune(PpsModel* m, const float* x, int N, int flags, void* stre
       std::vector<int> c;
       const bool h2ok = try_h2 && L.w2 && !L.planes_in && !L.planes_out && L.splitk == 1;
       if (L.op == Op::ConvPps) {
-        c = pps_tiles(*m, L, w->shapes.at(L.conv_output));
+        c = pps_tiles(L, w->shapes.at(L.conv_output));
         if (h2ok) {
           const size_t n = c.size();
           for (size_t i = 0; i < n; ++i)
@@ -1842,7 +1831,8 @@ int pps_model_autotune(PpsModel* m, const float* x, int N, int flags, void* stre
         // (base tile: the flags of an f16x2 candidate are or-ed in already;
         // the weight-stationary kernel has no tile order to choose)
         const int tb = tl & 0xff;
-        if (L.splitk == 1 && L.op != Op::Heads && tb >= GEMM_TILE_P_FIRST && tb != GEMM_TILE_WS)
+        if (L.splitk == 1 && L.op != Op::Heads && tile_lands_pipelined(tb) &&
+            tile_kind(tb) != TileKind::WS)
           for (int f : {PPS_TILE_B_TILED, PPS_TILE_COL_ORDER,
                         PPS_TILE_B_TILED | PPS_TILE_COL_ORDER})
             if (!(f & PPS_TILE_B_TILED) || (L.wt && !(tl & PPS_TILE_H2))) var.push_back(tl | f);

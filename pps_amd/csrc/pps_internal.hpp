@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/pps_abi.h"
+#include "gemm_tiles.hpp"  // enum GemmTile, tile_kind, the pipelined / patch tile tables
 
 namespace pps {
 
@@ -64,64 +65,6 @@ enum Epi {
                       // scaled by 2^s from their tensor's max and split into two f16
                       // terms, weights as two f16 planes, three MFMA terms)
 };
-enum GemmTile {
-  GEMM_TILE_AUTO = 0,
-  GEMM_TILE_128x128 = 1,
-  GEMM_TILE_128x64 = 2,
-  GEMM_TILE_64x128 = 3,
-  GEMM_TILE_64x64 = 4,
-  GEMM_TILE_256x128 = 5,
-  GEMM_TILE_128x128_K32 = 6,  // same shapes with a 32-wide K chunk per barrier
-  GEMM_TILE_128x64_K32 = 7,
-  GEMM_TILE_64x128_K32 = 8,
-  GEMM_TILE_64x64_K32 = 9,
-  GEMM_TILE_256x128_K32 = 10,
-  // 11..20: ids 1..10 with the bf16x3 kernel's A operand kept f32 in LDS
-  // 21..28 (bf16x3 kernel): 192x128 K16, 192x64 K16, 192x128 K32, 192x64 K32,
-  // then the same four with A kept f32 in LDS
-  GEMM_TILE_192_FIRST = 21,
-  // 29..35 (bf16x3 only): LDS-DMA pipelined kernel (gemm_x3p.hip), K chunk 32:
-  // 128x128, 192x128, 128x64, 192x64 (4 waves, 3 stages), 256x128, 128x256,
-  // 192x256 (8 waves, 2 stages)
-  GEMM_TILE_P_FIRST = 29,
-  // 36, 37: 128x128 and 192x128 with 8 waves
-  // 38..46 (bf16x3 only): ids 29..37 on 16x16x32 MFMA blocks (own rounding)
-  GEMM_TILE_P16_FIRST = 38,
-  // 47 (bf16x3 only, 16x16x32 rounding): 192x128 with 8 waves as 4 x 2 (48 x 64
-  // per wave) -- 256 tiles for the res5 layers' M = 12,288 x N = 512
-  GEMM_TILE_P16_192x128W42 = 47,
-  // 48, 49 (16x16x32): 192x64 (4 x 1 waves) and 96x128 (2 x 2 waves), 48 x 64
-  // per wave -- 256 tiles for M = 12,288 x N = 256 (res4 2a / 2b)
-  GEMM_TILE_P16_192x64W41 = 48,
-  GEMM_TILE_P16_96x128W22 = 49,
-  // 50 (16x16x32): 96x128 with 8 waves as 2 x 4 (48 x 32 per wave)
-  GEMM_TILE_P16_96x128W24 = 50,
-  // 51, 52 (16x16x32): 128x128 and 192x128 with 8 waves as 4 x 2 and three
-  // LDS stages (192x128 with plane activations: two)
-  GEMM_TILE_P16_128x128W42S3 = 51,
-  GEMM_TILE_P16_192x128W42S3 = 52,
-  // 53 (16x16x32): 96x128 with 8 waves as 2 x 4 and three LDS stages
-  GEMM_TILE_P16_96x128W24S3 = 53,
-  // 54 (16x16x32 rounding): weight-stationary persistent kernel
-  // (gemm_ws.hip) for 1x1 convs with K = 64 / 128 / 256; other shapes run
-  // tile 38
-  GEMM_TILE_WS = 54,
-  // 55 (16x16x32): 64x128 with 8 waves as 2 x 4 and four LDS stages -- short
-  // M (the 64-row head GEMMs: 248 split-K workgroups, three chunks in flight)
-  GEMM_TILE_P16_64x128W24S4 = 55,
-  // 56..59 (16x16x32, own rounding group: K in (channel chunk, tap) order):
-  // patch-staged stride-1 3x3 convs (gemm_x3c.hip) -- 192x128 (8 waves), 192x64 (4 waves), 96x128 (8 waves),
-  // 192x64 (8 waves); other shapes run tile 38
-  GEMM_TILE_C16_FIRST = 56,
-  GEMM_TILE_C16_192x128 = 56,
-  GEMM_TILE_C16_192x64 = 57,
-  GEMM_TILE_C16_96x128 = 58,
-  GEMM_TILE_C16_192x64W42 = 59,  // 192x64 with 8 waves (4 x 2)
-  // pipelined 16x16x32, 192x128 as 4 x 1 waves: f16x2 only (bf16x3 runs 47)
-  GEMM_TILE_P16_192x128W41 = 60,
-  GEMM_NUM_TILES = 61
-};
-
 struct GemmParams {
   // A operand: implicit im2col over an NHWC tensor (plain rows: H=1, W=M,
   // KH=KW=1).  Row m <-> output pixel (n, oh, ow).
@@ -226,15 +169,11 @@ struct GemmParams {
   const float* h2o_in;
   float h2o_bw, h2o_bb;
 };
-constexpr int kPpsFuseMaxStrips = 10;
-constexpr int kPpsFuseMaxCols = 256;  // widest tile the fused pooling takes (two column passes)
 
 int launch_gemm(const GemmParams& p, int epi, int batch, hipStream_t stream);
 int launch_gemm_x3(const GemmParams& p, int epi, int batch, hipStream_t stream);
 bool x3p_eligible(const GemmParams& p, int epi);
-int launch_gemm_x3p(const GemmParams& p, int epi, int batch, hipStream_t stream, int variant);
-int x3p_tile_rows(int tile, bool a3);  // rows (BM) of a pipelined tile id, 0 if none
-int x3p_tile_cols(int tile, bool a3);  // its columns (BN)
+int launch_gemm_x3p(const GemmParams& p, int epi, int batch, hipStream_t stream, int tile);
 int split_bf16x3(const float* x, int64_t n, int nbatch, uint16_t* out, hipStream_t stream);
 int row_sqnorm(const float* x, int64_t rows, int D, int64_t ld, float* out, hipStream_t stream);
 int split_sqnorm(const float* x, int64_t rows, int D, int64_t ld, uint16_t* out3, float* out,
@@ -246,8 +185,6 @@ bool ws_eligible(const GemmParams& p, int epi, int batch);
 int launch_gemm_ws(const GemmParams& p, int epi, hipStream_t stream);
 bool x3c_eligible(const GemmParams& p, int epi, int batch, int tile);
 int launch_gemm_x3c(const GemmParams& p, int epi, hipStream_t stream, int tile);
-int x3c_tile_rows(int tile);  // rows (BM) of a patch-staged tile id, 0 if none
-int x3c_tile_cols(int tile);
 
 // An activation-max slot (PPS_AMAX_SLOT_FLOATS floats, zeroed before its
 // producer runs): kAmaxSubs partial maxima kAmaxStride floats (256 B) apart,
@@ -292,30 +229,60 @@ __host__ __device__ inline float h2_scale_of(float amax, float* inv) {
 }
 
 // ---- op-level implementations behind the pps_conv* / pps_stem / pps_maxpool
-// entry points (abi.hip, stem.hip, feature_ops.hip), with the activation-max
+// entry points (conv_ops.hip, stem.hip, feature_ops.hip), with the activation-max
 // plumbing the whole-network plan uses (model.hip): amax_out (may be null)
 // receives max|y| of the launch's output; w_rs != null selects the f16x2
 // arithmetic (two-plane chunk-tiled weights w, per-channel scales w_rs, the
 // input tensors' maxima amax_in / amax_in2)
-int conv_impl(const float* x, int N, int H, int W, int Cin, int ldx, const void* w, int x3,
-              int Cout, int Kpad, int KH, int KW, int stride, int pad, int dil,
-              const float* scale, const float* shift, const float* residual, int relu, float* y,
-              int Ho, int Wo, int ldy, int tile, void* stream, const uint16_t* x_pl,
-              int64_t x_plane, uint16_t* y_pl, int64_t y_plane, int splitk, float* part,
-              int* fix_cnt, int64_t n_cnt, float* amax_out, const float* w_rs,
-              const float* amax_in, uint16_t* y_h2 = nullptr, int64_t y_h2_plane = 0,
-              const float* h2o_in = nullptr, float h2o_bw = 0.f, float h2o_bb = 0.f);
-int dual_impl(const float* x, int N, int H, int W, int Cin, int ldx, int KH, int KW, int stride,
-              int pad, const float* x2, int H2, int W2, int Cin2, int ldx2, int stride2,
-              const void* w, int x3, int Cout, int Kpad1, int Kpad2, const float* shift, int relu,
-              float* y, int Ho, int Wo, int ldy, int tile, void* stream, float* amax_out,
-              const float* w_rs, const float* amax_in, const float* amax_in2);
-int conv_pps_impl(const float* x, const uint16_t* x3, int64_t x_plane, int N, int H, int W,
-                  int Cin, int ldx, const uint16_t* w3, int Cout, int Kpad, int KH, int KW,
-                  int stride, int pad, int dil, const float* scale, const float* shift,
-                  const float* residual, float* y, int Ho, int Wo, const int32_t* splits, int S,
-                  int max_ave, float* pps_out, int tile, void* stream, const float* w_rs,
-                  const float* amax_in);
+struct ConvArgs {
+  // input: f32 NHWC x, or activation planes x_pl x_plane elements apart
+  // (three bf16 planes; with w_rs, two f16 planes)
+  const float* x = nullptr;
+  const uint16_t* x_pl = nullptr;
+  int64_t x_plane = 0;
+  int N = 0, H = 0, W = 0, Cin = 0, ldx = 0;
+  // weights: f32 [Cout][Kpad] (x3 = 0), bf16x3 planes (x3 = 1), or f16x2
+  // chunk-tiled planes with their per-channel scales w_rs
+  const void* w = nullptr;
+  int x3 = 0;
+  const float* w_rs = nullptr;
+  int Cout = 0, Kpad = 0, KH = 0, KW = 0, stride = 0, pad = 0, dil = 0;
+  // BN [+ residual] [+ ReLU]
+  const float *scale = nullptr, *shift = nullptr, *residual = nullptr;
+  int relu = 0;
+  // output, exactly one of: f32 y, bf16x3 planes y_pl, f16x2 planes y_h2 on
+  // the scale of the bound h2o_bw * max|x| + h2o_bb (max|x| from h2o_in)
+  float* y = nullptr;
+  uint16_t *y_pl = nullptr, *y_h2 = nullptr;
+  int64_t y_plane = 0, y_h2_plane = 0;
+  int Ho = 0, Wo = 0, ldy = 0;
+  int tile = 0;  // GemmTile, PPS_TILE_B_TILED / PPS_TILE_COL_ORDER or-ed in
+  void* stream = nullptr;
+  // conv split-K: partials [splitk][M][Cout]; with fix_cnt (n_cnt zeroed tile
+  // counters) in one launch, else raw partials + a summing pass
+  int splitk = 1;
+  float* part = nullptr;
+  int* fix_cnt = nullptr;
+  int64_t n_cnt = 0;
+  float* amax_out = nullptr;  // max|y| (with y_h2: the bound)
+  const float *amax_in = nullptr, *h2o_in = nullptr;  // f16x2: max|x|; the bound's max|x|
+  float h2o_bw = 0.f, h2o_bb = 0.f;
+  // conv_pps_impl: strip heights, max-or-average, the part-subset output
+  const int32_t* splits = nullptr;
+  int S = 0, max_ave = 0;
+  float* pps_out = nullptr;
+};
+// the fused-shortcut conv: the second operand (1x1, stride2, Kpad2 == Cin2
+// weight columns after the first Kpad) on top of ConvArgs (no scale, dil 1)
+struct DualArgs : ConvArgs {
+  const float *x2 = nullptr, *amax_in2 = nullptr;
+  int H2 = 0, W2 = 0, Cin2 = 0, ldx2 = 0, stride2 = 0, Kpad2 = 0;
+};
+int conv_impl(const ConvArgs& a);
+int conv_pps_impl(const ConvArgs& a);  // ldy = Cout, residual and ReLU always
+int dual_impl(const DualArgs& a);
+int splitk_impl(const float* x, int M, int K, const void* w, int x3, int Cout, int B, int splitk,
+                float* part, int tile, void* stream);
 int stem_conv_pool_x3(const float* x, int N, int H, const uint16_t* w3, const float* scale,
                       const float* shift, float* y, int Hc, int Hp, hipStream_t st, float* amax);
 int stem_conv_pool_h2(const float* x, int N, int H, const uint16_t* w2, const float* w_inv,

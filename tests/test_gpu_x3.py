@@ -428,6 +428,33 @@ def test_conv_x3_splitk_fused_bits(N, H, W, Cin, Cout, k, s, p, splitk, mode):
                               tile=45, splitk=splitk, part=part, counters=cnt[:0])
 
 
+def test_conv_x3_splitk_fused_rejects_non_fix_tiles():
+    """The one-launch split-K entry refuses, on the host and before any launch,
+    every pipelined tile that is not built with the one-launch epilogue
+    (ops.FIX_TILES): the tile counters stay zero.  (Ids 54 and 56-60 are
+    rerouted to another tile before that check.)"""
+    from pps_amd import model, ops
+    N, H, W, Cin, Cout, splitk = 1, 24, 8, 64, 128, 2
+    rng = np.random.RandomState(11)
+    x = _cuda(rng.randn(N, H, W, Cin).astype(np.float32))
+    w = (rng.randn(Cout, Cin, 1, 1) / np.sqrt(Cin)).astype(np.float32)
+    sc = _cuda(rng.uniform(0.5, 1.5, Cout).astype(np.float32))
+    sh = _cuda((rng.randn(Cout) * 0.1).astype(np.float32))
+    wp, kpad = model.pack_conv_weight(w)
+    w3 = ops.split_bf16x3(_cuda(wp))
+    part = torch.empty(splitk * N * H * W * Cout, device='cuda')
+    cnt = torch.zeros(4096, dtype=torch.int32, device='cuda')
+    y = torch.empty((N, H, W, Cout), device='cuda')
+    tiles = [t for t in list(range(29, 54)) + [55] if t not in ops.FIX_TILES]
+    assert len(tiles) == 21
+    for tile in tiles:
+        with pytest.raises(RuntimeError):
+            ops.conv2d_bn_act_x3p(x, Cin, w3, kpad, 1, 1, 0, 1, sc, sh, None, True, y,
+                                  tile=tile, splitk=splitk, part=part, counters=cnt)
+    torch.cuda.synchronize()
+    assert int(cnt.abs().sum()) == 0
+
+
 def test_forward_splitk_layers():
     """The model with split-K on the res5 convs (and plane edges) gives the
     one-pass features within the f32 forward tolerance."""

@@ -52,7 +52,7 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 def test_pipelined_tile_shapes():
     """pps_x3p_tile_shape (host-only) mirrors the pipelined tile table
-    (pps_internal.hpp): the ids the fused part pooling may use are exactly
+    (gemm_tiles.hpp): the ids the fused part pooling may use are exactly
     the 192-row tiles with <= 256 columns (192x256: f32 activations only)."""
     from pps_amd import ops
     want = {29: (128, 128), 30: (192, 128), 31: (128, 64), 32: (192, 64), 33: (256, 128),
@@ -60,10 +60,15 @@ def test_pipelined_tile_shapes():
             39: (192, 128), 40: (128, 64), 41: (192, 64), 42: (256, 128), 43: (128, 256),
             44: (128, 256), 45: (128, 128), 46: (192, 128), 47: (192, 128), 48: (192, 64),
             49: (96, 128), 50: (96, 128), 51: (128, 128), 52: (192, 128), 53: (96, 128),
-            55: (64, 128)}
+            55: (64, 128), 60: (192, 128)}
     assert ops.num_tiles() == 60
     for t, shape in want.items():
         assert ops.tile_shape(t) == shape, t
+        # plane activations: the same shape except on 35 (below)
+        assert ops.tile_shape(t, True) == (shape if t != 35 else (128, 256)), t
+    for t in range(0, ops.num_tiles() + 2):   # every other id: not a pipelined tile
+        if t not in want:
+            assert ops.tile_shape(t) == (0, 0) and ops.tile_shape(t, True) == (0, 0), t
     assert ops.tile_shape(28) == (0, 0) and ops.tile_shape(54) == (0, 0)  # 54: gemm_ws
     # plane activations: only the 192x256 8-wave tile falls back (to 128 rows:
     # two stages of it would not fit the LDS); the 192-row 8-wave and 96-row
@@ -74,8 +79,8 @@ def test_pipelined_tile_shapes():
     pps_f32 = [t for t in want if ops.tile_shape(t)[0] == 192 and ops.tile_shape(t)[1] <= 256]
     pps_pl = [t for t in want if ops.tile_shape(t, True)[0] == 192 and
               ops.tile_shape(t, True)[1] <= 256]
-    assert pps_f32 == [30, 32, 35, 37, 39, 41, 46, 47, 48, 52]
-    assert pps_pl == [30, 32, 37, 39, 41, 46, 47, 48, 52]
+    assert pps_f32 == [30, 32, 35, 37, 39, 41, 46, 47, 48, 52, 60]
+    assert pps_pl == [30, 32, 37, 39, 41, 46, 47, 48, 52, 60]
 
 
 def _defines():
