@@ -508,6 +508,25 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
                         void* workspace, int64_t ws_bytes,
                         float* vals, int32_t* idx, void* stream);
 
+/* pps_search_h2_tiled with an exclusion rule applied inside the kernel's
+ * filter: gallery row c is excluded for query r iff
+ *   q_group[r] >= 0 && g_group[c] == q_group[r]
+ * (q_group [Q], g_group [G]: int32 DEVICE arrays, both required -- a null
+ * pointer is PPS_ERR_INVALID_ARG and nothing is launched).  A negative query
+ * group excludes nothing; negative gallery groups are never excluded.  vals /
+ * idx [Q][k] = the stable (distance, index) top-k of the non-excluded rows,
+ * (+inf, -1) past their number: bit for bit pps_topk over the matrix
+ * pps_distmat_h2_tiled would write with the excluded cells set to +inf and
+ * the entries that landed on one turned into pads.  Every other argument,
+ * check and the workspace (pps_search_h2_workspace_bytes) are
+ * pps_search_h2_tiled's. */
+int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                             const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                             int D, int metric, int k, int segments, int tile,
+                             void* workspace, int64_t ws_bytes,
+                             float* vals, int32_t* idx,
+                             const int32_t* q_group, const int32_t* g_group, void* stream);
+
 /* k-reciprocal re-ranking (reid_dataset_evaluator.py:442-519): out [Q][G] =
  * re_ranking(q_g, q_q, g_g, k1, k2, lambda) with the reference's float32
  * operand order for V, V_qe and the Jaccard sums; ties in the initial rank use

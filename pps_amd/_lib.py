@@ -98,6 +98,9 @@ SIGNATURES = {
     'pps_topk_merge': [c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     'pps_search_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
                             c_int, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
+    'pps_search_h2_tiled_excl': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                                 c_int, c_int, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                 c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],

@@ -20,6 +20,13 @@
 // index) top-k is unique, so the result equals topk(distmat) bit for bit for
 // every tile and segment count.
 //
+// EXCL instantiations also drop, in the filter itself, the columns whose
+// group equals the row's non-negative group (SearchArgs::q_group / g_group):
+// an excluded column never enters a candidate buffer, because cuts and
+// thresholds are computed from buffer contents -- let in and removed at the
+// end, it could push a member of the true answer out at a cut.  The result is
+// the stable top-k of the remaining columns, padded with (+inf, -1).
+//
 // No workgroup waits on another: a work item touches only its own candidate
 // buffers (one set per launched workgroup, reused over the items the
 // workgroup strides through) and its own partial list.
@@ -49,6 +56,10 @@ struct SearchArgs {
   unsigned long long* cand;       // [slots][BM][cap]
   float* pvals;                   // [S][Q][k]
   int32_t* pidx;
+  // EXCL kernels only: column c is dropped for row r iff
+  // q_group[r] >= 0 && g_group[c] == q_group[r] (global row / column)
+  const int32_t* q_group;         // [Q]
+  const int32_t* g_group;         // [G]
 };
 
 // orders a wave's accesses to its candidate buffer in global memory (lane a's
@@ -76,7 +87,7 @@ __device__ inline unsigned long long uniform_u64(unsigned long long x) {
   return ((unsigned long long)hi << 32) | lo;
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+template <int BM, int BN, int WM, int WN, int NS, bool EXCL>
 __global__ void __launch_bounds__(64 * WM * WN)
 search_h2_kernel(GemmParams p, SearchArgs a) {
   using T = H2Tile<BM, BN, WM, WN, NS>;
@@ -155,6 +166,8 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
           const int gr = m0 + row;
           const float qn = p.norm_a[gr];
           const float ra = p.rs_a[gr];
+          int qg = -1;   // wave-uniform; negative excludes nothing
+          if constexpr (EXCL) qg = __builtin_amdgcn_readfirstlane(a.q_group[gr]);
           unsigned long long thr = uniform_u64(s_thr[row]);
           int n = __builtin_amdgcn_readfirstlane(s_n[row]);
           unsigned long long* buf = cand + (int64_t)row * cap;
@@ -172,7 +185,12 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
             const float d = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
             const unsigned long long packed =
                 ((unsigned long long)float_key(d) << 32) | (uint32_t)(n0 + c0h + c - cbase);
-            const bool take = ok[j] && packed <= thr;
+            bool take = ok[j] && packed <= thr;
+            // the group is loaded for survivors of the threshold only (no
+            // column codes held live over the rows)
+            if constexpr (EXCL) {
+              if (qg >= 0 && take) take = a.g_group[n0 + c0h + c] != qg;
+            }
             const unsigned long long bal = __ballot(take);
             if (take)
               buf[n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
@@ -275,10 +293,10 @@ static SearchLayout search_layout(int64_t Q, int64_t G, int k, int segments) {
   return L;
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+template <int BM, int BN, int WM, int WN, int NS, bool EXCL>
 static int launch_search(const GemmParams& p, SearchArgs a, hipStream_t st) {
   const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
-  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS, EXCL>), dim3((unsigned)grid),
                      dim3(64 * WM * WN), 0, st, p, a);
   PPS_CHECK_LAUNCH("search_h2_kernel");
   return PPS_OK;
@@ -298,11 +316,15 @@ int64_t pps_search_h2_workspace_bytes(int64_t Q, int64_t G, int k, int segments)
   return search_layout(Q, G, k, segments).total;
 }
 
-int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
-                        const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
-                        int D, int metric, int k, int segments, int tile, void* workspace,
-                        int64_t ws_bytes, float* vals, int32_t* idx, void* stream) {
+// pps_search_h2_tiled (excl false) and pps_search_h2_tiled_excl (excl true)
+static int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q,
+                           const float* qsq, const float* qrs, const uint16_t* g2t, const float* gsq,
+                           const float* grs, int64_t G, int D, int metric, int k, int segments,
+                           int tile, void* workspace, int64_t ws_bytes, float* vals,
+                           int32_t* idx, const int32_t* q_group, const int32_t* g_group,
+                           void* stream) {
   PPS_ENFORCE(vals && idx, "null pointer");
+  PPS_ENFORCE(!excl || (q_group && g_group), "null group pointer");
   PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
   PPS_ENFORCE(Q < (1ll << 31), "Q must fit int32");
   PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
@@ -326,7 +348,7 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
   PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
   const SearchLayout L = search_layout(Q, G, k, segments);
   if (!workspace || ws_bytes < L.total) {
-    set_error("pps_search_h2_tiled: workspace of " + std::to_string(ws_bytes) + " bytes, need " +
+    set_error(std::string(fn) + ": workspace of " + std::to_string(ws_bytes) + " bytes, need " +
               std::to_string(L.total));
     return PPS_ERR_CAPACITY;
   }
@@ -347,6 +369,8 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
   a.cand = reinterpret_cast<unsigned long long*>(ws);
   a.pvals = reinterpret_cast<float*>(ws + L.cand_bytes);
   a.pidx = reinterpret_cast<int32_t*>(ws + L.cand_bytes + (L.total - L.cand_bytes) / 2);
+  a.q_group = q_group;
+  a.g_group = g_group;
 
   GemmParams p{};
   p.splitk = 1;
@@ -360,10 +384,31 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
   p.rs_a = qrs; p.rs_b = grs;
   p.metric = metric;
 
-  const int rc = tile == 2 ? launch_search<192, 192, 2, 4, 3>(p, a, st)
-                           : launch_search<256, 256, 2, 4, 2>(p, a, st);
+  const int rc = excl ? (tile == 2 ? launch_search<192, 192, 2, 4, 3, true>(p, a, st)
+                                   : launch_search<256, 256, 2, 4, 2, true>(p, a, st))
+                      : (tile == 2 ? launch_search<192, 192, 2, 4, 3, false>(p, a, st)
+                                   : launch_search<256, 256, 2, 4, 2, false>(p, a, st));
   if (rc != PPS_OK) return rc;
   MergeOffsets offs{};
   for (int s = 0; s < a.S; ++s) offs.off[s] = (int64_t)s * a.tps * BN;
   return topk_merge(a.pvals, a.pidx, a.S, Q, k, offs, k, vals, idx, st);
+}
+
+int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                        const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                        int D, int metric, int k, int segments, int tile, void* workspace,
+                        int64_t ws_bytes, float* vals, int32_t* idx, void* stream) {
+  return search_h2_tiled("pps_search_h2_tiled", false, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
+                         metric, k, segments, tile, workspace, ws_bytes, vals, idx, nullptr,
+                         nullptr, stream);
+}
+
+int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                             const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                             int D, int metric, int k, int segments, int tile, void* workspace,
+                             int64_t ws_bytes, float* vals, int32_t* idx,
+                             const int32_t* q_group, const int32_t* g_group, void* stream) {
+  return search_h2_tiled("pps_search_h2_tiled_excl", true, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
+                         metric, k, segments, tile, workspace, ws_bytes, vals, idx, q_group,
+                         g_group, stream);
 }

@@ -185,9 +185,14 @@ class HipBackend(object):
         return ops.topk_merge(vals, idx, offsets, k)
 
     @staticmethod
-    def search(q, g, metric, k):
-        """Local rank list without the [Q, G] matrix (ops.search)."""
-        return ops.search(q, g, k, metric=metric)
+    def topk_excluding(dist, k, q_group, g_group):
+        return ops.topk_excluding(dist, k, q_group, g_group)
+
+    @staticmethod
+    def search(q, g, metric, k, q_group=None, g_group=None):
+        """Local rank list without the [Q, G] matrix (ops.search); q_group /
+        g_group: its exclusion rule, applied inside the kernel."""
+        return ops.search(q, g, k, metric=metric, q_group=q_group, g_group=g_group)
 
     @staticmethod
     def group_mean(x, groups):
@@ -206,6 +211,23 @@ class HipBackend(object):
     def rank_eval(dist, qid, gid, qcam, gcam):
         from .reid_dataset_evaluator import rank_eval
         return rank_eval(dist, qid, gid, qcam, gcam)
+
+
+def _topk_excluding_torch(dist, k, q_group, g_group):
+    """ops.topk_excluding in plain torch, for a backend without that method
+    (the CPU oracle backend: the collective logic then runs without a GPU):
+    stable (distance, index) top-k of the columns c with not (q_group[r] >= 0
+    and g_group[c] == q_group[r]), (+inf, -1) past their number."""
+    Q, G = dist.shape
+    mask = (g_group[None, :] == q_group[:, None]) & (q_group[:, None] >= 0)
+    vals, idx = torch.sort(dist.masked_fill(mask, float('inf')), dim=1, stable=True)
+    vals, idx = vals[:, :k].to(torch.float32), idx[:, :k]
+    hit = mask.gather(1, idx)
+    out_v = torch.full((Q, k), float('inf'), dtype=torch.float32, device=dist.device)
+    out_i = torch.full((Q, k), -1, dtype=torch.int32, device=dist.device)
+    out_v[:, :vals.shape[1]] = vals.masked_fill(hit, float('inf'))
+    out_i[:, :idx.shape[1]] = idx.masked_fill(hit, -1).to(torch.int32)
+    return out_v, out_i
 
 
 class ShardedEvaluator(object):
@@ -230,6 +252,7 @@ class ShardedEvaluator(object):
         self.qid_np, self.qcam_np = qid, qcam
         self.gid_np, self.gcam_np = gid[g0:g1], gcam[g0:g1]
         self._state = None
+        self._groups = {}
         dev = self.backend.device
         i32 = torch.int32
         self.qid = torch.from_numpy(qid.astype(np.int32)).to(dev)
@@ -300,22 +323,47 @@ class ShardedEvaluator(object):
             res['t_total_ms'] = evs[0].elapsed_time(evs[3])
         return res
 
-    def rank_list(self, q_local=None, g_local=None, k=100, dist=None, fused=False):
+    def exclusion_groups(self, by):
+        """(q_group, g_group) of ops.exclusion_groups for the global queries
+        and this rank's gallery shard, on the backend's device (built once)."""
+        if by not in ('id_cam', 'cam'):
+            raise RuntimeError("exclude must be None, 'id_cam' or 'cam', got %r" % (by,))
+        if by not in self._groups:
+            self._groups[by] = ops.exclusion_groups(self.qid_np, self.qcam_np, self.gid_np,
+                                                    self.gcam_np, by=by,
+                                                    device=self.backend.device)
+        return self._groups[by]
+
+    def rank_list(self, q_local=None, g_local=None, k=100, dist=None, fused=False,
+                  exclude=None):
         """Global stable top-k rank list [Q, k] (distances, global gallery
         indices) on every rank: local top-k, all-gather, k-way merge.
         fused=True (no `dist` given, a backend with `search`): the local list
         comes from the fused distance + top-k search, which never writes this
         shard's [Q, G] matrix; same result with a small fixed workspace.  Off by
         default: measured, the materialised path is the faster one (1.25x at the
-        Market shape, 1.04x at a 125k-row shard; DESIGN.md "Fused search")."""
+        Market shape, 1.04x at a 125k-row shard; DESIGN.md "Fused search").
+        exclude: None, 'id_cam' (drop the gallery rows that share the query's
+        id and camera: the junk rule every consumer of a rank list in the
+        reference applies first) or 'cam' (drop the query's whole camera:
+        separate_camera_set).  The list is then the stable top-k of the
+        remaining rows, (+inf, -1) past their number; the groups come from
+        the ids and cams the evaluator holds.  fused=True filters inside the
+        search kernel; otherwise the backend's topk_excluding runs on the
+        block (a plain-torch twin for a backend without one).  The merge is
+        the same: filtered lists merge like any others."""
         be = self.backend
         vals = idx = None
+        qg = gg = None
+        if exclude is not None:
+            qg, gg = self.exclusion_groups(exclude)
         if fused and dist is None and hasattr(be, 'search'):
             q_all = all_gather_rows(q_local, self.q_sizes)
             dev = q_all.device
             kin = min(k, g_local.shape[0])
             if kin > 0:
-                vals, idx = be.search(q_all, g_local, self.metric, kin)
+                vals, idx = (be.search(q_all, g_local, self.metric, kin) if qg is None else
+                             be.search(q_all, g_local, self.metric, kin, q_group=qg, g_group=gg))
         else:
             if dist is None:
                 q_all = all_gather_rows(q_local, self.q_sizes)
@@ -323,7 +371,12 @@ class ShardedEvaluator(object):
             dev = dist.device
             kin = min(k, dist.shape[1])
             if kin > 0:
-                vals, idx = be.topk(dist, kin)
+                if qg is None:
+                    vals, idx = be.topk(dist, kin)
+                elif hasattr(be, 'topk_excluding'):
+                    vals, idx = be.topk_excluding(dist, kin, qg, gg)
+                else:
+                    vals, idx = _topk_excluding_torch(dist, kin, qg, gg)
         if kin < k:   # short (or empty) shard: pad its list to k entries
             pv = torch.full((self.Q, k), float('inf'), dtype=torch.float32, device=dev)
             pi = torch.full((self.Q, k), -1, dtype=torch.int32, device=dev)

@@ -506,18 +506,104 @@ def _pad_list(vals, idx, k):
     return pv, pi
 
 
-def _search_one(q, q_split, index, k, metric, segments, tile, workspace):
+def exclusion_groups(qid, qcam, gid, gcam, by='id_cam', device='cuda'):
+    """(q_group [Q], g_group [G]) int32 tensors on `device` for the exclusion
+    rule of search / topk_excluding: dense non-negative codes (np.unique over
+    the query + gallery keys taken together, host numpy) such that q_group[i] ==
+    g_group[j] iff the keys are equal.  by='id_cam': key = (id, cam), the
+    reference's junk rule (reid_dataset_evaluator.py:327-331, :427);
+    by='cam': key = cam, the separate_camera_set rule (:332-333), which
+    contains the junk rule."""
+    qid, qcam, gid, gcam = (np.asarray(a).astype(np.int64).reshape(-1)
+                            for a in (qid, qcam, gid, gcam))
+    if len(qid) != len(qcam) or len(gid) != len(gcam):
+        raise RuntimeError('exclusion_groups: one id and one cam per row')
+    nq = len(qid)
+    dense = lambda a: np.asarray(np.unique(a, return_inverse=True)[1]).reshape(-1).astype(np.int64)
+    if by == 'id_cam':
+        # the pair as one key: dense id code x dense cam code (1-D sorts only)
+        ids, cams = dense(np.concatenate([qid, gid])), dense(np.concatenate([qcam, gcam]))
+        codes = dense(ids * (int(cams.max()) + 1 if len(cams) else 1) + cams)
+    elif by == 'cam':
+        codes = dense(np.concatenate([qcam, gcam]))
+    else:
+        raise RuntimeError("exclusion_groups: by must be 'id_cam' or 'cam', got %r" % (by,))
+    codes = np.ascontiguousarray(codes.astype(np.int32))
+    return (torch.from_numpy(codes[:nq].copy()).to(device),
+            torch.from_numpy(codes[nq:].copy()).to(device))
+
+
+def _check_groups(fn, q_group, g_group, Q, G, device):
+    """The (q_group, g_group) pair of an excluding call, or (None, None)."""
+    if q_group is None and g_group is None:
+        return None, None
+    if q_group is None or g_group is None:
+        raise RuntimeError('%s: q_group and g_group go together (both or neither)' % fn)
+    out = []
+    for name, t, n in (('q_group', q_group, Q), ('g_group', g_group, G)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError('%s: %s must be a torch.Tensor' % (fn, name))
+        if t.dtype != torch.int32:
+            raise RuntimeError('%s: %s must be int32, got %s' % (fn, name, t.dtype))
+        if t.dim() != 1 or t.shape[0] != n:
+            raise RuntimeError('%s: %s must have shape (%d,), got %s'
+                               % (fn, name, n, tuple(t.shape)))
+        if t.device != device:
+            raise RuntimeError('%s: %s is on %s, the search runs on %s'
+                               % (fn, name, t.device, device))
+        out.append(t if t.is_contiguous() else t.contiguous())
+    return out[0], out[1]
+
+
+def topk_excluding(dist, k, q_group, g_group):
+    """The materialised twin of search(..., q_group, g_group): the stable
+    (distance, index) top-k per row of `dist` [Q, G] over the columns c with
+    not (q_group[r] >= 0 and g_group[c] == q_group[r]) -> (vals [Q, k] f32,
+    idx [Q, k] i32), (+inf, -1) past their number.  pps_topk over a masked
+    COPY of the matrix (excluded cells +inf; `dist` is left as it is), the
+    entries that landed on an excluded cell turned into pads.  Holds a second
+    [Q, G] matrix and a [Q, G] byte mask while it runs."""
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 2:
+        raise RuntimeError('topk_excluding: dist must be a 2-D torch.Tensor')
+    Q, G = dist.shape
+    k = int(k)
+    if k < 1:
+        raise RuntimeError('topk_excluding: k must be >= 1')
+    q_group, g_group = _check_groups('topk_excluding', q_group, g_group, Q, G, dist.device)
+    if q_group is None:
+        raise RuntimeError('topk_excluding: q_group and g_group are required')
+    kin = min(k, G)
+    if kin == 0 or Q == 0:
+        return _pad_list(torch.empty((Q, 0), dtype=torch.float32, device=dist.device),
+                         torch.empty((Q, 0), dtype=torch.int32, device=dist.device), k)
+    mask = (g_group[None, :] == q_group[:, None]) & (q_group[:, None] >= 0)
+    masked = dist_buffer(Q, G, dist.device)
+    masked.copy_(dist)
+    masked.masked_fill_(mask, float('inf'))
+    vals, idx = topk(masked, kin)
+    del masked
+    hit = mask.gather(1, idx.long())
+    vals.masked_fill_(hit, float('inf'))
+    idx.masked_fill_(hit, -1)
+    return _pad_list(vals, idx, k)
+
+
+def _search_one(q, q_split, index, k, metric, segments, tile, workspace, q_group=None,
+                g_group=None):
     """One index: the fused kernel when it applies, else the matrix."""
     Q, D = q.shape
     G = index.shape[0]
     fused = (index.h2 is not None and q_split is not None and 1 <= k <= search_max_k())
-    if not fused:
+    if not fused or (q_group is not None and G == 0):
         kin = min(k, G)
         if kin == 0 or Q == 0:
             return _pad_list(torch.empty((Q, 0), dtype=torch.float32, device=q.device),
                              torch.empty((Q, 0), dtype=torch.int32, device=q.device), k)
         qc = q if q.is_contiguous() else q.contiguous()   # compute_dist takes whole rows
-        vals, idx = topk(compute_dist(qc, index, metric=metric, pad_rows=True), kin)
+        dist = compute_dist(qc, index, metric=metric, pad_rows=True)
+        if q_group is not None:
+            return topk_excluding(dist, k, q_group, g_group)
+        vals, idx = topk(dist, kin)
         return _pad_list(vals, idx, k)
     q2, qrs, qsq = q_split
     g2, grs, gsq = index.h2
@@ -530,15 +616,21 @@ def _search_one(q, q_split, index, k, metric, segments, tile, workspace):
                            '%d bytes (search_workspace_bytes)' % need)
     vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
-    call('pps_search_h2_tiled', _dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
-         _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
-         D, METRICS[metric], int(k), int(segments), int(tile), workspace.data_ptr(),
-         workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr(),
-         _stream())
+    args = (_dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
+            _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
+            D, METRICS[metric], int(k), int(segments), int(tile), workspace.data_ptr(),
+            workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr())
+    if q_group is None:
+        call('pps_search_h2_tiled', *(args + (_stream(),)))
+    else:
+        call('pps_search_h2_tiled_excl', *(args + (_dev(q_group, 'q_group', torch.int32),
+                                                   _dev(g_group, 'g_group', torch.int32),
+                                                   _stream())))
     return vals, idx
 
 
-def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None):
+def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None,
+           q_group=None, g_group=None):
     """The k nearest gallery rows of every query -> (vals [Q, k] float32,
     idx [Q, k] int32), ascending, ties by gallery index, (+inf, -1) past G
     entries: exactly topk(compute_dist(q, gallery, math='h2'), k), from a
@@ -562,7 +654,22 @@ def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None
     matrix -- when the fused kernel does not apply: an index holding an x3
     split (also one the constructor downgraded from a requested 'h2'),
     D % 32 != 0, non-contiguous queries (copied to whole rows first), or
-    k > search_max_k() (up to pps_topk's 1024)."""
+    k > search_max_k() (up to pps_topk's 1024).
+
+    q_group [Q] / g_group [G] (int32 tensors on the queries' device, both or
+    neither; g_group covers the whole logical gallery, each segment of a
+    sequence gets its slice): gallery row c is excluded for query r iff
+    q_group[r] >= 0 and g_group[c] == q_group[r] (exclusion_groups builds the
+    reference's junk and separate-camera rules; arange on both sides is
+    "exclude myself").  The rule runs inside the kernel's filter
+    (pps_search_h2_tiled_excl), so the rows are the stable top-k of the
+    non-excluded gallery rows, (+inf, -1) past their number -- exactly
+    topk_excluding(compute_dist(q, gallery, math='h2'), k, q_group, g_group)
+    (in a self-search, the matrix of compute_dist(..., symmetric=False): the
+    mirrored self-distance kernel copies its upper triangle, other bits than
+    the general kernel's below the diagonal).
+    The fallback cases above then run compute_dist + topk_excluding, which
+    materialises the matrix, a masked copy of it and a byte mask."""
     if isinstance(gallery, GalleryIndex):
         parts = [gallery]
     elif isinstance(gallery, torch.Tensor):
@@ -581,6 +688,9 @@ def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None
     if k < 1:
         raise RuntimeError('search: k must be >= 1')
     D = q.shape[1]
+    starts = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+    q_group, g_group = _check_groups('search', q_group, g_group, q.shape[0], int(starts[-1]),
+                                     q.device)
     if q.shape[0] == 0:
         return (torch.empty((0, k), dtype=torch.float32, device=q.device),
                 torch.empty((0, k), dtype=torch.int32, device=q.device))
@@ -588,10 +698,12 @@ def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None
     if (D % 32 == 0 and q.is_contiguous() and k <= search_max_k() and
             any(p.h2 is not None for p in parts)):
         q_split = split_h2_tiled(q)   # once, as compute_dist splits them
-    lists = [_search_one(q, q_split, p, k, metric, segments, tile, workspace) for p in parts]
+    lists = [_search_one(q, q_split, p, k, metric, segments, tile, workspace, q_group,
+                         None if g_group is None else g_group[int(a):int(a) + p.shape[0]])
+             for p, a in zip(parts, starts[:-1])]
     if len(lists) == 1:
         return lists[0]
-    offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])[:-1]]).astype(np.int64)
+    offsets = starts[:-1]
     if offsets[-1] + parts[-1].shape[0] >= 2 ** 31:
         raise RuntimeError('search: gallery indices must fit int32')
     # merge rounds: each call takes at most R lists with R * k <= 8192, R <= 64;

@@ -149,6 +149,71 @@ def cmc(distmat, query_ids=None, gallery_ids=None, query_cams=None, gallery_cams
     return ret, valid.astype(np.float64)
 
 
+def first_match_cmc(idx, query_ids, gallery_ids, valid, topk):
+    """The reference's first_match_break booking (:340-355) from rank lists
+    that already left the excluded gallery rows out: idx [Q, >= topk] global
+    gallery indices in rank order (-1 = pad), valid [Q] the queries that have
+    a true match at all.  A valid query books one hit at the first list
+    position < topk whose gallery id is its own (none: its match ranks past
+    topk and the row stays zero, as at :348-349).  -> rows [Q, topk], cumsum
+    applied."""
+    idx = np.asarray(idx)
+    qid, gid = np.asarray(query_ids), np.asarray(gallery_ids)
+    valid = np.asarray(valid).astype(bool)
+    if idx.ndim != 2 or idx.shape[0] != len(qid) or idx.shape[1] < topk:
+        raise ValueError('first_match_cmc: lists of shape %s for %d queries and topk=%d'
+                         % (tuple(idx.shape), len(qid), topk))
+    idx = idx[:, :topk].astype(np.int64)
+    ret = np.zeros((len(qid), topk))
+    if len(gid) and topk:
+        match = (idx >= 0) & (gid[np.maximum(idx, 0)] == qid[:, None])
+        rows = np.nonzero(valid & match.any(axis=1))[0]
+        ret[rows, match[rows].argmax(axis=1)] = 1
+    return ret.cumsum(axis=1)
+
+
+def cmc_from_search(query_feats, gallery, query_ids=None, gallery_ids=None, query_cams=None,
+                    gallery_cams=None, topk=100, separate_camera_set=False,
+                    metric='euclidean', average=True, first_match_break=True):
+    """cmc(..., first_match_break=True) (:283-363) without a distance matrix:
+    the excluding fused search (ops.search with the junk rule, or the
+    separate-camera rule, as its exclusion groups) returns every query's
+    topk best valid gallery rows; the first one carrying the query's id books
+    the hit (first_match_cmc); query validity -- some gallery row has the
+    query's id and is not excluded -- comes from the ids and cams alone.  Same
+    outputs and the same 'No valid query' error as cmc.  gallery: anything
+    ops.search takes (a [G, D] array or tensor, a GalleryIndex, a sequence of
+    them).  ops.search's fallback cases (an x3 index, D % 32 != 0, strided
+    queries, topk > ops.search_max_k()) DO materialise the matrix.  The
+    fractional mode (first_match_break=False) needs list depths topk does not
+    bound and is rejected, not approximated: use cmc."""
+    if not first_match_break:
+        raise RuntimeError('cmc_from_search computes the first-match CMC only '
+                           '(first_match_break=True): the fractional CMC needs every true '
+                           "match's rank, which a top-%d list does not bound; use cmc" % topk)
+    qid, qcam = _host_ids(query_ids), _host_ids(query_cams)
+    gid, gcam = _host_ids(gallery_ids), _host_ids(gallery_cams)
+    if not isinstance(gallery, (ops.GalleryIndex, list, tuple)):
+        gallery = _to_dev(gallery)
+    q = _to_dev(query_feats)
+    # valid: same-id gallery rows minus the same-(id, cam) ones (both rules keep
+    # exactly the same-id rows of other cameras)
+    junk = ops.exclusion_groups(qid, qcam, gid, gcam, 'id_cam', 'cpu')
+    qj, gj = (t.numpy() for t in junk)
+    qi, gi = (t.numpy() for t in ops.exclusion_groups(qid, qid, gid, gid, 'cam', 'cpu'))
+    count = lambda g, at: np.bincount(g, minlength=int(at.max()) + 1 if len(at) else 1)[at]
+    valid = (count(gi, qi) - count(gj, qj)) > 0
+    if not valid.any():
+        raise RuntimeError('No valid query')
+    q_group, g_group = (t.to(q.device) for t in junk) if not separate_camera_set else \
+        ops.exclusion_groups(qid, qcam, gid, gcam, 'cam', q.device)
+    _, idx = ops.search(q, gallery, topk, metric=metric, q_group=q_group, g_group=g_group)
+    ret = first_match_cmc(idx.cpu().numpy(), qid, gid, valid, topk)
+    if average:
+        return np.sum(ret, axis=0) / valid.sum()
+    return ret, valid.astype(np.float64)
+
+
 SGS_MAX_IDS = 16384   # pps_sgs_keys / pps_sgs_groups (include/pps_abi.h)
 
 

@@ -15,13 +15,38 @@ events; medians.  Features: normalised Gaussian, seed 0.  One JSON line per
 shape, with max|vals_A - vals_B| and idx equality on the timed inputs (0 /
 true by construction).
 
+--exclude replaces those legs by the group-excluding ones at the same two
+shapes, with synthetic Market-like labels (751 ids x 6 cams over the gallery,
+queries drawn from the same ids, the junk rule as exclusion groups):
+
+  B   the unfiltered ops.search -- from the library --parent-lib names (a
+      libpps_hip.so built from the commit to compare against; its
+      pps_search_h2_tiled is called on the same operands), else this build's
+  B'  ops.search(..., q_group, g_group) of this build; and to say what of
+      B' - B costs what: B0 = this build's unfiltered search, B'off = the
+      excluding kernel with every query group -1 (its fixed part: the code
+      shape and the row's group read), B'miss = gallery groups no query has
+      (every survivor's group load, nothing excluded)
+  A'  ops.compute_dist into a preallocated buffer, then ops.topk_excluding
+
+alternating in one process under the same repetition scheme (B and B' on the
+tile and segment count one timed sweep of the unfiltered search picks), with
+peaks; and, at the shard shape, the matrix-free first-match CMC
+(reid_dataset_evaluator.cmc_from_search, topk = k) against cmc(
+first_match_break=True) on the materialised matrix: wall clock around a
+device synchronize (both have host parts), peaks, equality of the curves.
+
   python scripts/bench_search.py [--reps 5] [--shapes market,shard] [--segmented]
+                                 [--exclude [--parent-lib PATH]]
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
+import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -154,16 +179,190 @@ def bench_segmented(Q, G, D, k, reps, ops):
                 idx_max=int(idx.max()), sorted=bool((vals[:, 1:] >= vals[:, :-1]).all()))
 
 
+def _market_labels(Q, G):
+    """751 ids x 6 cams over the gallery, queries drawn from the same ids."""
+    rng = np.random.RandomState(0)
+    return (rng.randint(0, 751, Q), rng.randint(0, 6, Q),
+            rng.randint(0, 751, G), rng.randint(0, 6, G))
+
+
+def _parent_search(path):
+    """ops.search's single-index fused call on another build's library: the
+    queries split by this build (split_h2_tiled is the same kernel), then that
+    library's pps_search_h2_tiled."""
+    from pps_amd import _lib, ops
+    L = ctypes.CDLL(path)
+    fn = L.pps_search_h2_tiled
+    fn.argtypes = _lib.SIGNATURES['pps_search_h2_tiled']
+    fn.restype = ctypes.c_int
+
+    def search(q, index, k, segments, tile, workspace):
+        Q, D = q.shape
+        G = index.shape[0]
+        q2, qrs, qsq = ops.split_h2_tiled(q)
+        g2, grs, gsq = index.h2
+        vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+        idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+        rc = fn(q2.data_ptr(), Q, qsq.data_ptr(), qrs.data_ptr(), g2.data_ptr(), gsq.data_ptr(),
+                grs.data_ptr(), G, D, 0, k, segments, tile, workspace.data_ptr(),
+                workspace.numel(), vals.data_ptr(), idx.data_ptr(),
+                torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError('parent pps_search_h2_tiled failed (status %d)' % rc)
+        return vals, idx
+    return search
+
+
+def _wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def bench_exclude(name, Q, G, D, k, reps, ops, parent_lib=None, cmc=False):
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(0)
+    q, gal = _feats(Q, D, gen), _feats(G, D, gen)
+    index = ops.GalleryIndex(gal, math='h2')
+    qid, qcam, gid, gcam = _market_labels(Q, G)
+    qg, gg = ops.exclusion_groups(qid, qcam, gid, gcam, by='id_cam')
+    excluded = float((torch.bincount(gg, minlength=int(max(qg.max(), gg.max())) + 1)[qg.long()])
+                     .double().mean())
+    out = ops.dist_buffer(Q, G, 'cuda')
+
+    best_a = None
+    for t in range(ops.h2_num_tiles()):
+        ops.compute_dist(q, index, out=out, math='h2', tile=t)
+        ms, _ = _time(lambda: ops.compute_dist(q, index, out=out, math='h2', tile=t))
+        if best_a is None or ms < best_a[1]:
+            best_a = (t, ms)
+    tile_a = best_a[0]
+    seg_cands = [0, 1, 2, 4, 8, 16]
+    ws = torch.empty((max(ops.search_workspace_bytes(Q, G, k, s) for s in seg_cands),),
+                     dtype=torch.uint8, device='cuda')
+    best_b = None
+    for t in range(1, ops.search_num_tiles()):
+        for s in seg_cands:
+            ops.search(q, index, k, segments=s, tile=t, workspace=ws)
+            ms, _ = _time(lambda: ops.search(q, index, k, segments=s, tile=t, workspace=ws))
+            if best_b is None or ms < best_b[2]:
+                best_b = (t, s, ms)
+    tile_b, seg_b = best_b[0], best_b[1]
+    parent = _parent_search(parent_lib) if parent_lib else None
+
+    def path_b():
+        if parent is not None:
+            return parent(q, index, k, seg_b, tile_b, ws)
+        return ops.search(q, index, k, segments=seg_b, tile=tile_b, workspace=ws)
+
+    def path_bx():
+        return ops.search(q, index, k, segments=seg_b, tile=tile_b, workspace=ws, q_group=qg,
+                          g_group=gg)
+
+    def path_ax():
+        ops.compute_dist(q, index, out=out, math='h2', tile=tile_a)
+        return ops.topk_excluding(out, k, qg, gg)
+
+    qg_off, gg_miss = torch.full_like(qg, -1), gg + (int(qg.max()) + 1)
+    parts = dict(
+        search_this_build=lambda: ops.search(q, index, k, segments=seg_b, tile=tile_b,
+                                             workspace=ws),
+        search_excl_off=lambda: ops.search(q, index, k, segments=seg_b, tile=tile_b, workspace=ws,
+                                           q_group=qg_off, g_group=gg),
+        search_excl_miss=lambda: ops.search(q, index, k, segments=seg_b, tile=tile_b,
+                                            workspace=ws, q_group=qg, g_group=gg_miss))
+    for f in (path_b, path_bx, path_ax) + tuple(parts.values()):
+        f()
+    tb, tbx, tax = [], [], []
+    tparts = dict((n, []) for n in parts)
+    for _ in range(max(reps, 5)):
+        ms, rb = _time(path_b)
+        tb.append(ms)
+        ms, rbx = _time(path_bx)
+        tbx.append(ms)
+        ms, rax = _time(path_ax)
+        tax.append(ms)
+        for n, f in parts.items():
+            tparts[n].append(_time(f)[0])
+    diff = float((rax[0] - rbx[0]).nan_to_num(posinf=0.).abs().max())
+    same = bool(torch.equal(rax[1], rbx[1]))
+    plain_same = bool(torch.equal(rb[1], ops.search(q, index, k, segments=seg_b, tile=tile_b,
+                                                    workspace=ws)[1]))
+    del out, rax
+    torch.cuda.empty_cache()
+
+    def alloc_ax():
+        o = ops.dist_buffer(Q, G, 'cuda')
+        ops.compute_dist(q, index, out=o, math='h2', tile=tile_a)
+        ops.topk_excluding(o, k, qg, gg)
+    peak_ax = _peak(alloc_ax)
+    del ws
+    torch.cuda.empty_cache()
+    peak_bx = _peak(lambda: ops.search(q, index, k, segments=seg_b, tile=tile_b, q_group=qg,
+                                       g_group=gg))
+    b_ms, bx_ms, ax_ms = _median(tb), _median(tbx), _median(tax)
+    res = dict(shape=name, leg='exclude', Q=Q, G=G, D=D, k=k,
+               unfiltered_from='parent library' if parent is not None else 'this build',
+               excluded_rows_per_query=round(excluded, 2),
+               search_ms=round(b_ms, 3), search_excl_ms=round(bx_ms, 3),
+               materialised_excl_ms=round(ax_ms, 3),
+               excl_over_unfiltered=round(bx_ms / b_ms, 4),
+               excl_over_materialised=round(bx_ms / ax_ms, 4),
+               materialised_tile=tile_a, search_tile=tile_b, search_segments=seg_b,
+               search_excl_peak_bytes=int(peak_bx), materialised_excl_peak_bytes=int(peak_ax),
+               max_abs_vals_diff=diff, idx_equal=same, unfiltered_idx_equal_this_build=plain_same,
+               search_ms_all=[round(x, 3) for x in tb],
+               search_excl_ms_all=[round(x, 3) for x in tbx],
+               materialised_excl_ms_all=[round(x, 3) for x in tax])
+    for n, t in tparts.items():
+        res[n + '_ms'] = round(_median(t), 3)
+        res[n + '_ms_all'] = [round(x, 3) for x in t]
+    if cmc:
+        from pps_amd import reid_dataset_evaluator as gev
+
+        def from_search():
+            return gev.cmc_from_search(q, index, qid, gid, qcam, gcam, topk=k)
+
+        def from_matrix():
+            d = ops.compute_dist(q, index, math='h2', tile=tile_a, pad_rows=True)
+            return gev.cmc(d, qid, gid, qcam, gcam, topk=k, first_match_break=True)
+
+        from_search()
+        from_matrix()
+        ts, tm = [], []
+        for _ in range(max(reps, 5)):
+            ms, cs = _wall(from_search)
+            ts.append(ms)
+            ms, cm = _wall(from_matrix)
+            tm.append(ms)
+        torch.cuda.empty_cache()
+        res.update(cmc_from_search_ms=round(_median(ts), 3), cmc_matrix_ms=round(_median(tm), 3),
+                   cmc_from_search_peak_bytes=int(_peak(from_search)),
+                   cmc_matrix_peak_bytes=int(_peak(from_matrix)),
+                   cmc_equal=bool(np.array_equal(cs, cm)), cmc_rank1=float(cs[0]),
+                   cmc_from_search_ms_all=[round(x, 3) for x in ts],
+                   cmc_matrix_ms_all=[round(x, 3) for x in tm])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--shapes', default='market,shard')
     ap.add_argument('--segmented', action='store_true')
+    ap.add_argument('--exclude', action='store_true')
+    ap.add_argument('--parent-lib', default=None)
     a = ap.parse_args()
     from pps_amd import ops
     for name in [s for s in a.shapes.split(',') if s]:
         Q, G, D, k = SHAPES[name]
-        print(json.dumps(bench_shape(name, Q, G, D, k, a.reps, ops)), flush=True)
+        if a.exclude:
+            print(json.dumps(bench_exclude(name, Q, G, D, k, a.reps, ops, a.parent_lib,
+                                           cmc=name == 'shard')), flush=True)
+        else:
+            print(json.dumps(bench_shape(name, Q, G, D, k, a.reps, ops)), flush=True)
         torch.cuda.empty_cache()
     if a.segmented:
         print(json.dumps(bench_segmented(*SEGMENTED, a.reps, ops)), flush=True)
