@@ -326,54 +326,20 @@ int pps_pairwise_distance(const float* X, int N, int D, float* Z,
  * Count-based mAP/CMC (reid_dataset_evaluator.py:283-363 `cmc`, :366-439
  * `mean_ap`): identical to sorting each row with a stable (distance, index)
  * order, without materialising the sort.  Gallery may be a shard
- * [g_offset, g_offset+G) of a global gallery.
- *
- * 1) pps_collect_positives: for each query row, list the gallery entries that
- *    are true matches (gid == qid && gcam != qcam), as (distance, global
- *    gallery index), in index order.  pos_cnt[q] may exceed Pmax, in which
- *    case only Pmax entries are stored and the caller must retry larger. */
-int pps_collect_positives(const float* dist, int64_t Q, int64_t G,
-                          int64_t ldd, const int32_t* qid,
-                          const int32_t* qcam, const int32_t* gid,
-                          const int32_t* gcam, int64_t g_offset, int Pmax,
-                          float* pos_d, int32_t* pos_idx, int32_t* pos_cnt,
-                          void* stream);
-/* 2) pps_rank_counts: R positive lists ([R][Q][Pmax] entries, counts
- *    [R][Q]) are merged and sorted per query by (distance, index) into
- *    sorted_d [Q][R*Pmax] / sorted_idx (padding +inf / -1; pos_total[q] =
- *    merged count); then for every valid gallery entry of
- *    THIS shard (not same id & same cam) its distance is binned against the
- *    sorted positives: hist[q][p] += 1 where p = first positive with
- *    d_p >= d_i, and before[q] counts entries ordered before the first
- *    positive.  hist / before are ADDITIVE over gallery shards (sum with an
- *    all-reduce), and must be zeroed by the caller.  Capacity: R*Pmax <=
- *    2048 (LDS), else PPS_ERR_CAPACITY -- the streaming entry points below
- *    have no such limit and are what the Python evaluator uses. */
-int pps_rank_counts(const float* dist, int64_t Q, int64_t G, int64_t ldd,
-                    const int32_t* qid, const int32_t* qcam,
-                    const int32_t* gid, const int32_t* gcam, int64_t g_offset,
-                    int R, int Pmax, const float* pos_d,
-                    const int32_t* pos_idx, const int32_t* pos_cnt,
-                    float* sorted_d, int32_t* sorted_idx, int32_t* pos_total,
-                    int32_t* hist, int32_t* before, void* stream);
-/* 3) pps_ap_finalize: per query AP (sklearn >= 0.19 step-wise definition,
- *    tie-grouped), validity flag and first-match rank from the summed
- *    counts.  ap is float64 [Q]; first_rank int32 [Q] (-1 when invalid). */
-int pps_ap_finalize(int64_t Q, int Ptot, const float* sorted_d,
-                    const int32_t* pos_total, const int32_t* hist,
-                    const int32_t* before, double* ap, int32_t* valid,
-                    int32_t* first_rank, void* stream);
-
-/* Streaming evaluation (the product path): the same counts as 1)-2) from a
- * per-identity gallery index, with one pure stream over the distance row.
+ * [g_offset, g_offset+G) of a global gallery.  A query's true
+ * matches come from a per-identity gallery index, and the counting pass is
+ * one pure stream over the distance row.
  *
  * a) pps_collect_matches: members = the shard's LOCAL gallery indices sorted
  *    by (id, index) (a CSR over identities, built once per gallery from the
  *    ids); query q's identity occupies members[q_beg[q], q_end[q]).  Lists
- *    its positives (other camera) as pps_collect_positives does, and its junk
+ *    its positives (same id, other camera) as (distance, global gallery
+ *    index) in pos_d / pos_idx [Q][Pmax], in index order, and its junk
  *    entries (same id, same camera, reid_dataset_evaluator.py:427-428) as
- *    junk_d / junk_idx [Q][Jmax] with exact counts junk_cnt -- O(matches)
- *    per query instead of a scan of G ids.
+ *    junk_d / junk_idx [Q][Jmax] -- O(matches) per query instead of a scan
+ *    of G ids.  pos_cnt / junk_cnt are the exact counts: one above Pmax /
+ *    Jmax means only that many entries were stored and the caller must
+ *    retry larger.
  * b) pps_rank_prepare: merge R shards' lists [R][Q][Pmax] and sort by
  *    (distance, global index) -> sorted_d / sorted_idx [Q][R*Pmax] (padding
  *    +inf / -1), pos_total [Q], and the query's bin-lookup cells
@@ -383,13 +349,21 @@ int pps_ap_finalize(int64_t Q, int Ptot, const float* sorted_d,
  *    query's lists are sorted in place in its sorted_d / sorted_idx row in
  *    global memory (same order; slower, for identities with thousands of
  *    gallery entries per shard).  No capacity limit (R*Pmax < 2^30).
- * c) pps_rank_count_stream: for this shard's rows, hist[q][p] += #entries
- *    with p = first positive d_p >= d, before[q] += #entries ordered before
- *    the first positive, over all entries of the row minus this shard's junk
- *    entries -- the same additive counts as pps_rank_counts (caller zeroes
- *    hist / before; sum over shards), then pps_ap_finalize.  Rows are read
- *    as 16-byte vectors when 16-byte aligned (ldd % 4 == 0).  No capacity
- *    limit on Ptot (long positive lists are searched in L2). */
+ * c) pps_rank_count_stream: every entry of THIS shard's rows, minus the
+ *    shard's junk entries, is binned by distance against the query's sorted
+ *    positives: hist[q][p] += 1 where p = the first positive with d_p >= d,
+ *    and before[q] += 1 for an entry ordered before the first positive.
+ *    hist [Q][Ptot] / before [Q] are ADDITIVE over gallery shards (sum with
+ *    an all-reduce) and must be zeroed by the caller.  Rows are read as
+ *    16-byte vectors when 16-byte aligned (ldd % 4 == 0).  No capacity
+ *    limit on Ptot (long positive lists are searched in L2).
+ * d) pps_ap_finalize: per query AP (sklearn >= 0.19 step-wise definition,
+ *    tie-grouped), validity flag and first-match rank from the summed
+ *    counts.  ap is float64 [Q]; first_rank int32 [Q] (-1 when invalid). */
+int pps_ap_finalize(int64_t Q, int Ptot, const float* sorted_d,
+                    const int32_t* pos_total, const int32_t* hist,
+                    const int32_t* before, double* ap, int32_t* valid,
+                    int32_t* first_rank, void* stream);
 int pps_collect_matches(const float* dist, int64_t Q, int64_t G, int64_t ldd,
                         const int32_t* qcam, const int32_t* gcam, const int32_t* members,
                         const int32_t* q_beg, const int32_t* q_end, int64_t g_offset,

@@ -1,9 +1,13 @@
 """ORACLE (test infrastructure only) -- NumPy restatement of the count-based
-rank evaluation kernels in pps_amd/csrc/rank.hip, used as a CPU backend so the
-gallery-sharded collective logic (pps_amd/distributed.py) can be tested with
-torch.distributed gloo, world_size > 1, without a GPU.  Same semantics as the
-HIP kernels: positives = same id & different cam; junk = same id & same cam;
+rank evaluation kernels in pps_amd/csrc/eval_counts.hip, used as a CPU backend
+so the gallery-sharded collective logic (pps_amd/distributed.py) can be tested
+with torch.distributed gloo, world_size > 1, without a GPU.  Same semantics as
+the HIP kernels: positives = same id & different cam; junk = same id & same cam;
 stable (distance, global gallery index) order; counts additive over shards.
+It needs no gallery index: CpuBackend.collect_positives scans the ids and cams
+for what collect_matches lists from the index, and CpuBackend.rank_counts
+computes what rank_prepare + rank_count_stream do (junk skipped by id and cam
+instead of being taken back out).
 """
 import numpy as np
 import torch

@@ -68,11 +68,6 @@ SIGNATURES = {
                                         c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_int,
                                         c_int, c_ptr, c_ptr, c_int, c_ptr],
-    'pps_collect_positives': [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                              c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
-    'pps_rank_counts': [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
-                        c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                        c_ptr, c_ptr],
     'pps_collect_matches': [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                             c_i64, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                             c_ptr],

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <string>
 
-#include "pps_internal.hpp"
+#include "retrieval.hpp"
 
 namespace pps {
 
@@ -19,52 +19,6 @@ bool debug_sync() {
   }();
   return on;
 }
-
-int part_power_set(const float*, int, int, int, int, const int32_t*, int, int, float*,
-                   hipStream_t);
-int l2_normalize(const float*, int64_t, int, float*, hipStream_t);
-int group_mean(const float*, int, const int32_t*, const int32_t*, int, float*, hipStream_t);
-int collect_positives(const float*, int64_t, int64_t, int64_t, const int32_t*,
-                      const int32_t*, const int32_t*, const int32_t*, int64_t, int, float*,
-                      int32_t*, int32_t*, hipStream_t);
-int rank_counts(const float*, int64_t, int64_t, int64_t, const int32_t*, const int32_t*,
-                const int32_t*, const int32_t*, int64_t, int, int, const float*,
-                const int32_t*, const int32_t*, float*, int32_t*, int32_t*, int32_t*,
-                int32_t*, hipStream_t);
-int ap_finalize(int64_t, int, const float*, const int32_t*, const int32_t*,
-                const int32_t*, double*, int32_t*, int32_t*, hipStream_t);
-int topk(const float*, int64_t, int64_t, int64_t, int, float*, int32_t*, hipStream_t);
-int argsort_rows(const float*, int64_t, int64_t, int64_t, int32_t*, int64_t, float*, int64_t,
-                 hipStream_t);
-int argsort_rows_cap();
-int sgs_keys(const int32_t*, int64_t, int64_t, int64_t, const int32_t*, const int32_t*,
-             const int32_t*, const int32_t*, int, int, float*, hipStream_t);
-int sgs_groups(const float*, const int32_t*, int64_t, int64_t, int, const int32_t*, int32_t*,
-               int32_t*, int32_t*, int32_t*, hipStream_t);
-int sgs_ranks(const int32_t*, int64_t, const int32_t*, int64_t, const int32_t*, const int32_t*,
-              const int32_t*, const int32_t*, int, int, const int32_t*, int64_t, int32_t*,
-              hipStream_t);
-size_t sgs_groups_lds_bytes(int64_t, int);
-int cmc_counts(const float*, int64_t, int64_t, int64_t, int64_t, int, const float*,
-               const int32_t*, const int32_t*, const int32_t*, const int32_t*, int,
-               const float*, const int32_t*, const int32_t*, int32_t*, hipStream_t);
-int cmc_finalize(int64_t, int, const int32_t*, const int32_t*, int, int, double*, int32_t*,
-                 hipStream_t);
-int collect_matches(const float*, int64_t, int64_t, const int32_t*, const int32_t*,
-                    const int32_t*, const int32_t*, const int32_t*, int64_t, int, float*,
-                    int32_t*, int32_t*, int, float*, int32_t*, int32_t*, hipStream_t);
-int rank_prepare(int, int64_t, int, const float*, const int32_t*, const int32_t*, float*,
-                 int32_t*, int32_t*, int32_t*, hipStream_t);
-int rank_count_stream(const float*, int64_t, int64_t, int64_t, int64_t, int, const float*,
-                      const int32_t*, const int32_t*, const int32_t*, int, const float*,
-                      const int32_t*, const int32_t*, int32_t*, int32_t*, hipStream_t);
-int rerank(const float*, int64_t, const float*, int64_t, const float*, int64_t, int64_t, int64_t,
-           int, int, double, void*, size_t, float*, hipStream_t, int);
-size_t rerank_workspace_bytes(int64_t, int64_t, int, int);
-size_t rerank_workspace_bytes_for(const float*, int64_t, const float*, int64_t, const float*,
-                                  int64_t, int64_t, int64_t, int, int, int);
-int splitk_bn_act_normalize(const float*, int, int64_t, int, int, const float*,
-                            const float*, int, int, float*, hipStream_t);
 
 }  // namespace pps
 
@@ -327,38 +281,6 @@ int pps_pairwise_distance(const float* X, int N, int D, float* Z, void* stream) 
   return launch_gemm(p, EPI_DIST, 1, as_stream(stream));
 }
 
-int pps_collect_positives(const float* dist, int64_t Q, int64_t G, int64_t ldd,
-                          const int32_t* qid, const int32_t* qcam, const int32_t* gid,
-                          const int32_t* gcam, int64_t g_offset, int Pmax, float* pos_d,
-                          int32_t* pos_idx, int32_t* pos_cnt, void* stream) {
-  PPS_ENFORCE(dist && qid && qcam && gid && gcam && pos_d && pos_idx && pos_cnt,
-              "null pointer");
-  PPS_ENFORCE(Q >= 0 && G >= 0 && ldd >= G && Pmax > 0, "bad shape");
-  return collect_positives(dist, Q, G, ldd, qid, qcam, gid, gcam, g_offset, Pmax, pos_d,
-                           pos_idx, pos_cnt, as_stream(stream));
-}
-
-int pps_rank_counts(const float* dist, int64_t Q, int64_t G, int64_t ldd,
-                    const int32_t* qid, const int32_t* qcam, const int32_t* gid,
-                    const int32_t* gcam, int64_t g_offset, int R, int Pmax,
-                    const float* pos_d, const int32_t* pos_idx, const int32_t* pos_cnt,
-                    float* sorted_d, int32_t* sorted_idx, int32_t* pos_total,
-                    int32_t* hist, int32_t* before, void* stream) {
-  PPS_ENFORCE(dist && qid && qcam && gid && gcam && pos_d && pos_idx && pos_cnt &&
-                  sorted_d && sorted_idx && pos_total && hist && before,
-              "null pointer");
-  PPS_ENFORCE(Q >= 0 && G >= 0 && ldd >= G, "bad shape");
-  PPS_ENFORCE(R >= 1 && R <= 64, "R must be in [1, 64]");
-  if ((int64_t)R * Pmax > 2048) {
-    set_error("merged positives per query R*Pmax=" + std::to_string((int64_t)R * Pmax) +
-              " exceeds the LDS capacity 2048");
-    return PPS_ERR_CAPACITY;
-  }
-  return rank_counts(dist, Q, G, ldd, qid, qcam, gid, gcam, g_offset, R, Pmax, pos_d,
-                     pos_idx, pos_cnt, sorted_d, sorted_idx, pos_total, hist, before,
-                     as_stream(stream));
-}
-
 int pps_collect_matches(const float* dist, int64_t Q, int64_t G, int64_t ldd,
                         const int32_t* qcam, const int32_t* gcam, const int32_t* members,
                         const int32_t* q_beg, const int32_t* q_end, int64_t g_offset,
@@ -374,7 +296,7 @@ int pps_collect_matches(const float* dist, int64_t Q, int64_t G, int64_t ldd,
                          as_stream(stream));
 }
 
-int pps_rank_cells(void) { return 1024; }
+int pps_rank_cells(void) { return kRankCells; }
 
 int pps_rank_prepare(int R, int64_t Q, int Pmax, const float* pos_d, const int32_t* pos_idx,
                      const int32_t* pos_cnt, float* sorted_d, int32_t* sorted_idx,
@@ -382,7 +304,8 @@ int pps_rank_prepare(int R, int64_t Q, int Pmax, const float* pos_d, const int32
   PPS_ENFORCE(pos_d && pos_idx && pos_cnt && sorted_d && sorted_idx && pos_total && cells,
               "null pointer");
   PPS_ENFORCE(((uintptr_t)cells & 15) == 0, "cells must be 16-byte aligned");
-  PPS_ENFORCE(R >= 1 && R <= kMergeMaxLists, "R must be in [1, 64]");
+  PPS_ENFORCE(R >= 1 && R <= kMergeMaxLists,
+              "R must be in [1, " + std::to_string(kMergeMaxLists) + "]");
   PPS_ENFORCE(Q >= 0 && Pmax > 0, "bad shape");
   // beyond kRankMergeCap merged positives the lists are sorted in place in
   // global memory (rank_prepare_global_kernel): no capacity limit
@@ -450,7 +373,8 @@ int pps_cmc_finalize(int64_t Q, int Ptot, const int32_t* pos_total, const int32_
 int pps_topk(const float* dist, int64_t Q, int64_t G, int64_t ldd, int k, float* vals,
              int32_t* idx, void* stream) {
   PPS_ENFORCE(dist && vals && idx, "null pointer");
-  PPS_ENFORCE(k >= 1 && k <= 1024, "k must be in [1, 1024], got " + std::to_string(k));
+  PPS_ENFORCE(k >= 1 && k <= kTopkCap,
+              "k must be in [1, " + std::to_string(kTopkCap) + "], got " + std::to_string(k));
   PPS_ENFORCE(G >= k && ldd >= G, "need G >= k");
   PPS_ENFORCE(G < (1ll << 31), "G must fit int32");
   return topk(dist, Q, G, ldd, k, vals, idx, as_stream(stream));
@@ -472,7 +396,8 @@ int pps_sgs_keys(const int32_t* order, int64_t Q, int64_t G, int64_t ldo, const 
                  int separate_camera_set, int U, float* keys, void* stream) {
   PPS_ENFORCE(order && gid && gcam && qid && qcam && keys, "null pointer");
   PPS_ENFORCE(Q >= 0 && G >= 0 && ldo >= G, "bad shape");
-  PPS_ENFORCE(U >= 1 && U <= 16384, "U (distinct gallery identities) must be in [1, 16384]");
+  PPS_ENFORCE(U >= 1 && U <= kSgsMaxIds, "U (distinct gallery identities) must be in [1, " +
+                                                  std::to_string(kSgsMaxIds) + "]");
   return sgs_keys(order, Q, G, ldo, gid, gcam, qid, qcam, separate_camera_set ? 1 : 0, U, keys,
                   as_stream(stream));
 }
@@ -484,8 +409,9 @@ int pps_sgs_groups(const float* sorted_keys, const int32_t* perm, int64_t Q, int
   PPS_ENFORCE(Q >= 0 && G >= 1 && G <= argsort_rows_cap(), "G must be in [1, " +
                                                                std::to_string(argsort_rows_cap()) +
                                                                "]");
-  PPS_ENFORCE(U >= 1 && U <= 16384, "U (distinct gallery identities) must be in [1, 16384]");
-  PPS_ENFORCE(sgs_groups_lds_bytes(G, U) <= 160 * 1024, "groups do not fit in LDS");
+  PPS_ENFORCE(U >= 1 && U <= kSgsMaxIds, "U (distinct gallery identities) must be in [1, " +
+                                                  std::to_string(kSgsMaxIds) + "]");
+  PPS_ENFORCE(sgs_groups_lds_bytes(G, U) <= kLdsBytesGfx950, "groups do not fit in LDS");
   return sgs_groups(sorted_keys, perm, Q, G, U, qid, gstart, glen, nids, qt, as_stream(stream));
 }
 
@@ -496,7 +422,7 @@ int pps_sgs_ranks(const int32_t* perm, int64_t Q, int64_t G, const int32_t* rows
   PPS_ENFORCE(perm && gstart && glen && nids && qt && k && (nr == 0 || (rows && draws)),
               "null pointer");
   PPS_ENFORCE(Q >= 0 && G >= 1 && nr >= 0 && repeat >= 1 && ldd >= 1, "bad shape");
-  PPS_ENFORCE(U >= 1 && U <= 16384 && ldd <= U, "ldd must be in [1, U]");
+  PPS_ENFORCE(U >= 1 && U <= kSgsMaxIds && ldd <= U, "ldd must be in [1, U]");
   return sgs_ranks(perm, G, rows, nr, gstart, glen, nids, qt, U, repeat, draws, ldd, k,
                    as_stream(stream));
 }
@@ -508,8 +434,9 @@ int pps_topk_merge(const float* vals, const int32_t* idx, int R, int64_t Q, int 
   PPS_ENFORCE(R >= 1 && R <= kMergeMaxLists,
               "R must be in [1, " + std::to_string(kMergeMaxLists) + "]");
   PPS_ENFORCE(Q >= 0 && k_in >= 1 && k_out >= 1, "bad shape");
-  PPS_ENFORCE((int64_t)R * k_in <= 8192,
-              "R * k_in must be <= 8192 (LDS), got " + std::to_string((int64_t)R * k_in));
+  PPS_ENFORCE((int64_t)R * k_in <= kMergeMaxEntries,
+              "R * k_in must be <= " + std::to_string(kMergeMaxEntries) + " (LDS), got " +
+                  std::to_string((int64_t)R * k_in));
   MergeOffsets offs{};
   for (int r = 0; r < R; ++r) {
     PPS_ENFORCE(list_offsets[r] >= 0 && list_offsets[r] + k_in <= (int64_t)INT32_MAX,
@@ -546,7 +473,7 @@ int pps_re_ranking_ld(const float* q_g, int64_t ld_qg, const float* q_q, int64_t
   PPS_ENFORCE(K1 + K1 * Kh <= 1024, "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
   PPS_ENFORCE(k2 * (K1 + K1 * Kh <= 256 ? 256 : (K1 + K1 * Kh <= 512 ? 512 : 1024)) <= 4096,
               "k2 * V row capacity must be <= 4096");
-  PPS_ENFORCE(jaccard_lds_bytes(G) + 2048 <= 160 * 1024,
+  PPS_ENFORCE(jaccard_lds_bytes(G) + 2048 <= kLdsBytesGfx950,
               "G must be <= 38400 (the Jaccard pass keeps a gallery row in LDS)");
   PPS_ENFORCE((Q + G) >= K1, "need Q + G >= k1 + 1");
   PPS_ENFORCE((flags & ~(PPS_RERANK_SYMMETRIC | PPS_RERANK_WHOLE)) == 0,

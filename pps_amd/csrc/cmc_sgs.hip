@@ -20,7 +20,7 @@
 //  5. sgs_ranks: per query and repeat, pick[t] = perm[gstart[t] + draw[t]];
 //     k = #{t : pick[t] < pick[query identity]} = the reference's
 //     `np.nonzero(matches[i, sampled])[0]` (one hit per repeat).
-#include "pps_internal.hpp"
+#include "retrieval.hpp"
 
 namespace pps {
 

@@ -300,6 +300,16 @@ int maxpool2d(const float* x, int N, int H, int W, int C, int k, int stride, int
 int split_act_h2(const float* x, int64_t n, const float* slot, uint16_t* planes, int64_t plane,
                  hipStream_t st);
 int amax_of(const float* x, int64_t n, float* amax, hipStream_t st);
+// feature head (feature_ops.hip): part pooling, row normalisation, group means
+// and the split-K heads' summing epilogue
+int part_power_set(const float* x, int N, int H, int W, int C, const int32_t* splits, int S,
+                   int max_ave, float* out, hipStream_t st);
+int l2_normalize(const float* x, int64_t N, int D, float* y, hipStream_t st);
+int group_mean(const float* x, int D, const int32_t* offsets, const int32_t* members,
+               int ngroups, float* out, hipStream_t st);
+int splitk_bn_act_normalize(const float* part, int S, int64_t sstride, int M, int N,
+                            const float* scale, const float* shift, int relu, int normalize,
+                            float* y, hipStream_t st);
 
 // ---- f16x2 distance GEMM (gemm_h2.hip) ---------------------------------------
 constexpr int kH2NumTiles = 8;
@@ -325,70 +335,5 @@ struct SeamParams {
 };
 bool seam_supported(int K1, int N1, int N2);
 int launch_seam_x3(const SeamParams& p, int K1, int N1, int N2, hipStream_t st);
-
-// ---- retrieval (rank.hip) ---------------------------------------------------
-constexpr int kMergeMaxLists = 64;
-// rank_count_stream / cmc_counts: gallery entries per workgroup (grid.y =
-// chunks of a row, <= 65535)
-#ifndef RANK_STREAM_U
-#define RANK_STREAM_U 8   // float4 per thread in flight in the rank streams
-#endif
-constexpr int kRankStreamChunk = 256 * 4 * RANK_STREAM_U;
-// rank_prepare merges R*Pmax positives in dynamic LDS (4 int arrays):
-// 16 B per merged positive, 128 KiB at the cap -- within gfx950's 160 KiB
-// LDS per workgroup (this library is built for gfx950 only)
-constexpr int kRankMergeCap = 8192;
-constexpr int kLdsBytesGfx950 = 160 * 1024;
-static_assert(16 * kRankMergeCap <= kLdsBytesGfx950, "rank_prepare LDS exceeds the CU's LDS");
-struct MergeOffsets {  // kernel-argument copy of the per-list global offsets
-  int64_t off[kMergeMaxLists];
-};
-int topk_merge(const float* vals, const int32_t* idx, int R, int64_t Q, int kin,
-               const MergeOffsets& offs, int kout, float* out_vals, int32_t* out_idx,
-               hipStream_t st);
-
-// ---- re-ranking (rerank.hip) -------------------------------------------------
-// The concatenated distance matrix M = [[q_q, q_g], [q_g^T, g_g]]
-// (reid_dataset_evaluator.py:447-452) read in place from its blocks (row
-// strides ld*; qgT = q_g transposed, [G][ldT]), and for a SYMMETRIC M (q_q,
-// g_g exactly symmetric) the normalised square of :452-454,
-// OD[i][j] = M[j][i]^2 / colmax[i] = M[i][j]^2 / colmax[i], computed on the fly
-// with the arithmetic of the OD-building kernels (rr_od).
-// OD's arithmetic, float32 as NumPy does it (np.power(M, 2) then / colmax):
-// a rounded square and an IEEE (correctly rounded) division -- spelled with
-// the _rn intrinsics so that every kernel computing it gives the same bits
-// (a plain `/` may be lowered to a reciprocal-based approximation)
-// (m * m) / cm, both rounded (a product feeding a division cannot fuse)
-// dynamic LDS of the Jaccard pass for a gallery of G (rerank.hip)
-size_t jaccard_lds_bytes(int64_t G);
-
-__device__ inline float rr_od(float m, float cm) { return (m * m) / cm; }
-
-struct RrMatrix {
-  const float* qg;
-  const float* qq;
-  const float* gg;
-  const float* qgT;
-  int64_t ldqg, ldqq, ldgg, ldT, Q, G;
-  const float* colmax;
-  __device__ float m(int64_t r, int64_t c) const {
-    if (r < Q) return c < Q ? qq[r * ldqq + c] : qg[r * ldqg + (c - Q)];
-    return c < Q ? qgT[(r - Q) * ldT + c] : gg[(r - Q) * ldgg + (c - Q)];
-  }
-  __device__ float od(int64_t i, int64_t j) const {
-    return rr_od(m(i, j), colmax[i]);
-  }
-};
-// stable (value, index) top-k of every row of OD (symmetric M, rows of N =
-// Q + G >= 16384 entries, every block 16-byte aligned): the wave-streaming
-// top-k reading M's blocks in place (no N x N OD buffer)
-int topk_rr(const RrMatrix& M, int k, float* vals, int32_t* idx, hipStream_t st);
-// symmetric M with colmax not yet known: rowmax[q] = max of row q's squares
-// (= column q's), and the top-k by (OD, index) through a top-(k+8) on m * m
-// (rank.hip); scratch of topk_rr_sq_scratch_bytes(N, k)
-int topk_rr_sq(const RrMatrix& M, int k, float* rowmax, void* scratch, size_t scratch_bytes,
-               float* vals, int32_t* idx, hipStream_t st);
-size_t topk_rr_sq_scratch_bytes(int64_t N, int k);
-bool topk_rr_eligible(const RrMatrix& M, int k);
 
 }  // namespace pps

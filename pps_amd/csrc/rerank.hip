@@ -12,14 +12,14 @@
 //
 //  1. rerank_colmax_sq / rowmax_sq / build_od : OD[i][j] = M[j][i]^2 / max_r M[r][i]^2
 //     with M = [[qq, qg], [qg^T, gg]]                          (:447-454)
-//  2. pps_topk (rank.hip) on OD, k = k1 + 1 -> initial_rank      (:456)
+//  2. pps_topk (topk.hip) on OD, k = k1 + 1 -> initial_rank      (:456)
 //  3. rerank_v_rows  : k-reciprocal sets, expansion, exp weights  (:462-488)
 //  4. rerank_vqe     : V_qe[i] = mean of V rows initial_rank[i,:k2] (:490-494)
 //  5. rerank_csc_*   : inverted index of V_qe                     (:497-499)
 //  6. rerank_jaccard : temp_min, jaccard, lambda blend, [Q][G] out (:501-518)
 #include <vector>
 
-#include "pps_internal.hpp"
+#include "retrieval.hpp"
 
 // NumPy rounds every float32 product and sum on its own; hipcc's default
 // fp-contract=fast would fuse e.g. the final blend jac * (1 - l) + od * l
@@ -794,8 +794,6 @@ rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_
     out[i * (N - Q) + (j - Q)] = wj + wo;
   }
 }
-
-int topk(const float*, int64_t, int64_t, int64_t, int, float*, int32_t*, hipStream_t);
 
 namespace {
 struct RrLayout {  // V-row capacities of a (k1, k2) configuration

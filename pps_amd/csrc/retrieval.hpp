@@ -1,0 +1,135 @@
+// The retrieval side of libpps_hip.so: every internal function one translation
+// unit calls in another (evaluation counts, top-k, row argsort, the
+// single-gallery-shot CMC, re-ranking) and every capacity limit that both a
+// kernel file and an entry-point guard (abi.hip, search_h2.hip) depend on --
+// each named once, here.
+#pragma once
+#include "pps_internal.hpp"
+
+namespace pps {
+
+// ---- limits -------------------------------------------------------------------
+// LDS per workgroup (this library is built for gfx950 only)
+constexpr int kLdsBytesGfx950 = 160 * 1024;
+constexpr int kTopkCap = 1024;       // topk: largest k
+constexpr int kTkwMinRow = 16384;    // rows at least this long take topk_wave_kernel
+constexpr int kTkwMaxK = 256;        // ... for k up to this (also the fused search's largest k)
+constexpr int kMergeMaxLists = 64;   // topk_merge / rank_prepare: lists (shards) per query
+// topk_merge keeps the R * k_in packed entries of a query in dynamic LDS (8 B each)
+constexpr int kMergeMaxEntries = 8192;
+constexpr int kRankCells = 1024;     // bin-lookup cells per query (pps_rank_cells)
+// rank_count_stream / cmc_counts: gallery entries per workgroup (grid.y =
+// chunks of a row, <= 65535)
+constexpr int kRankStreamU = 8;      // float4 per thread in flight in the rank streams
+constexpr int kRankStreamChunk = 256 * 4 * kRankStreamU;
+// rank_prepare merges R*Pmax positives in dynamic LDS (4 int arrays):
+// 16 B per merged positive, 128 KiB at the cap
+constexpr int kRankMergeCap = 8192;
+static_assert(16 * kRankMergeCap <= kLdsBytesGfx950, "rank_prepare LDS exceeds the CU's LDS");
+// sgs_groups keeps two int32 bounds per gallery identity in LDS (plus G / 4 bytes)
+constexpr int kSgsMaxIds = 16384;
+static_assert(8 * kSgsMaxIds <= kLdsBytesGfx950, "sgs_groups LDS exceeds the CU's LDS");
+
+// ---- evaluation counts (eval_counts.hip) ----------------------------------------
+int collect_matches(const float* dist, int64_t Q, int64_t ldd, const int32_t* qcam,
+                    const int32_t* gcam, const int32_t* members, const int32_t* q_beg,
+                    const int32_t* q_end, int64_t g_offset, int Pmax, float* pos_d,
+                    int32_t* pos_idx, int32_t* pos_cnt, int Jmax, float* junk_d,
+                    int32_t* junk_idx, int32_t* junk_cnt, hipStream_t st);
+int rank_prepare(int R, int64_t Q, int Pmax, const float* pos_d, const int32_t* pos_idx,
+                 const int32_t* pos_cnt, float* sorted_d, int32_t* sorted_idx,
+                 int32_t* pos_total, int32_t* cells, hipStream_t st);
+int rank_count_stream(const float* dist, int64_t Q, int64_t G, int64_t ldd, int64_t g_offset,
+                      int Ptot, const float* sorted_d, const int32_t* sorted_idx,
+                      const int32_t* pos_total, const int32_t* cells, int Jmax, const float* junk_d,
+                      const int32_t* junk_idx, const int32_t* junk_cnt, int32_t* hist,
+                      int32_t* before, hipStream_t st);
+int ap_finalize(int64_t Q, int Ptot, const float* sorted_d, const int32_t* pos_total,
+                const int32_t* hist, const int32_t* before, double* ap, int32_t* valid,
+                int32_t* first_rank, hipStream_t st);
+int cmc_counts(const float* dist, int64_t Q, int64_t G, int64_t ldd, int64_t g_offset, int Ptot,
+               const float* sorted_d, const int32_t* sorted_idx, const int32_t* pos_total,
+               const int32_t* qcam, const int32_t* gcam, int Jmax, const float* junk_d,
+               const int32_t* junk_idx, const int32_t* junk_cnt, int32_t* hist,
+               hipStream_t st);
+int cmc_finalize(int64_t Q, int Ptot, const int32_t* pos_total, const int32_t* hist, int topk,
+                 int fmb, double* ret, int32_t* valid, hipStream_t st);
+
+// ---- stable top-k (topk.hip) ----------------------------------------------------
+int topk(const float* dist, int64_t Q, int64_t G, int64_t ldd, int k, float* vals,
+         int32_t* idx, hipStream_t st);
+struct MergeOffsets {  // kernel-argument copy of the per-list global offsets
+  int64_t off[kMergeMaxLists];
+};
+int topk_merge(const float* vals, const int32_t* idx, int R, int64_t Q, int kin,
+               const MergeOffsets& offs, int kout, float* out_vals, int32_t* out_idx,
+               hipStream_t st);
+
+// ---- row argsort (rowsort.hip) --------------------------------------------------
+int argsort_rows(const float* dist, int64_t Q, int64_t G, int64_t ldd, int32_t* idx,
+                 int64_t ldi, float* vals, int64_t ldv, hipStream_t st);
+int argsort_rows_cap();
+
+// ---- CMC with single_gallery_shot (cmc_sgs.hip) ---------------------------------
+int sgs_keys(const int32_t* order, int64_t Q, int64_t G, int64_t ldo, const int32_t* gid,
+             const int32_t* gcam, const int32_t* qid, const int32_t* qcam, int sep, int U,
+             float* keys, hipStream_t st);
+int sgs_groups(const float* skeys, const int32_t* perm, int64_t Q, int64_t G, int U,
+               const int32_t* qid, int32_t* gstart, int32_t* glen, int32_t* nids, int32_t* qt,
+               hipStream_t st);
+int sgs_ranks(const int32_t* perm, int64_t G, const int32_t* rows, int64_t nr,
+              const int32_t* gstart, const int32_t* glen, const int32_t* nids, const int32_t* qt,
+              int U, int repeat, const int32_t* draws, int64_t ldd, int32_t* kout,
+              hipStream_t st);
+size_t sgs_groups_lds_bytes(int64_t G, int U);
+
+// ---- re-ranking (rerank.hip) -------------------------------------------------
+int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const float* gg,
+           int64_t ldgg, int64_t Q, int64_t G, int k1, int k2, double lambda, void* ws,
+           size_t ws_bytes, float* out, hipStream_t st, int flags);
+size_t rerank_workspace_bytes(int64_t Q, int64_t G, int k1, int k2);
+size_t rerank_workspace_bytes_for(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq,
+                                  const float* gg, int64_t ldgg, int64_t Q, int64_t G, int k1,
+                                  int k2, int flags);
+// dynamic LDS of the Jaccard pass for a gallery of G
+size_t jaccard_lds_bytes(int64_t G);
+
+// OD's arithmetic, float32 as NumPy does it (np.power(M, 2) then / colmax):
+// (m * m) / cm, both rounded (a product feeding a division cannot fuse), the
+// same expression in every kernel that computes it so that all give the same bits
+__device__ inline float rr_od(float m, float cm) { return (m * m) / cm; }
+
+// The concatenated distance matrix M = [[q_q, q_g], [q_g^T, g_g]]
+// (reid_dataset_evaluator.py:447-452) read in place from its blocks (row
+// strides ld*; qgT = q_g transposed, [G][ldT]), and for a SYMMETRIC M (q_q,
+// g_g exactly symmetric) the normalised square of :452-454,
+// OD[i][j] = M[j][i]^2 / colmax[i] = M[i][j]^2 / colmax[i], computed on the fly
+// with the arithmetic of the OD-building kernels (rr_od).
+struct RrMatrix {
+  const float* qg;
+  const float* qq;
+  const float* gg;
+  const float* qgT;
+  int64_t ldqg, ldqq, ldgg, ldT, Q, G;
+  const float* colmax;
+  __device__ float m(int64_t r, int64_t c) const {
+    if (r < Q) return c < Q ? qq[r * ldqq + c] : qg[r * ldqg + (c - Q)];
+    return c < Q ? qgT[(r - Q) * ldT + c] : gg[(r - Q) * ldgg + (c - Q)];
+  }
+  __device__ float od(int64_t i, int64_t j) const {
+    return rr_od(m(i, j), colmax[i]);
+  }
+};
+// stable (value, index) top-k of every row of OD (symmetric M, rows of N =
+// Q + G >= kTkwMinRow entries, every block 16-byte aligned): the wave-streaming
+// top-k reading M's blocks in place (no N x N OD buffer)
+int topk_rr(const RrMatrix& M, int k, float* vals, int32_t* idx, hipStream_t st);
+// symmetric M with colmax not yet known: rowmax[q] = max of row q's squares
+// (= column q's), and the top-k by (OD, index) through a top-(k+8) on m * m
+// (topk.hip); scratch of topk_rr_sq_scratch_bytes(N, k)
+int topk_rr_sq(const RrMatrix& M, int k, float* rowmax, void* scratch, size_t scratch_bytes,
+               float* vals, int32_t* idx, hipStream_t st);
+size_t topk_rr_sq_scratch_bytes(int64_t N, int k);
+bool topk_rr_eligible(const RrMatrix& M, int k);
+
+}  // namespace pps

@@ -28,7 +28,7 @@
 // from the row (L2-resident between passes), sorted by the core and
 // written at its offset.
 // Algorithmic bytes per row: G * 4 read + G * 4 written (+ G * 4 with vals).
-#include "pps_internal.hpp"
+#include "retrieval.hpp"
 
 namespace pps {
 
@@ -49,9 +49,8 @@ constexpr int kNF2 = kNF / 2;
 #endif
 constexpr int kSample = PPS_SORT_SAMPLE;   // the coarse histogram counts every kSample-th word
 constexpr int kNet = 16;     // buckets up to this size: one lane's sorting network
-constexpr int kLds = 160 * 1024;
 constexpr int kFixed = 4 * (kNC + 1) + 4 * kNF2 + 8 * 2 * kW + 64;
-constexpr int kSortU = (kLds - kFixed) / 8 / kT;   // row entries per thread
+constexpr int kSortU = (kLdsBytesGfx950 - kFixed) / 8 / kT;   // row entries per thread
 constexpr int kSortCap = kSortU * kT;              // longest row of the one-pass kernel
 // long rows: segments of <= kSeg words (src + dst in LDS), grouped by
 // kHalf-word histogram prefixes, at most kSegCap per row

@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "gemm_h2_common.hpp"
+#include "retrieval.hpp"
 #include "topk_wave_common.hpp"
 
 namespace pps {
@@ -101,7 +102,7 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
   static_assert(BNH % WCOLS == 0, "a wave's columns fall in one pass");
   static_assert(NW * kTkwMaxK * 8 <= T::LDS_BYTES, "sort scratch of the waves");
   constexpr int STATE = T::LDS_BYTES;      // row state beside the stages / the parked tile
-  static_assert(STATE % 16 == 0 && STATE + BM * 16 <= 160 * 1024, "LDS");
+  static_assert(STATE % 16 == 0 && STATE + BM * 16 <= kLdsBytesGfx950, "LDS");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[STATE + BM * 16];
   unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(lds + STATE);
   int* s_n = reinterpret_cast<int*>(lds + STATE + BM * 8);
@@ -253,7 +254,8 @@ static void search_tile_shape(int tile, int& BM, int& BN) {
 // Segment count before it is rounded to whole tiles per segment: the request
 // (0 = auto: panels x S fills the CUs once or twice, whichever leaves the
 // smaller idle tail) under the clamps -- the segment's tile count, and
-// topk_merge's 64 lists and 8192 merged entries.  Non-decreasing in G.
+// topk_merge's kMergeMaxLists lists and kMergeMaxEntries merged entries.
+// Non-decreasing in G.
 static int search_segments(int64_t Q, int64_t G, int k, int segments, int BM, int BN) {
   const int64_t panels = std::max<int64_t>(cdiv(Q, BM), 1), tiles_n = std::max<int64_t>(cdiv(G, BN), 1);
   int64_t S = segments;
@@ -268,7 +270,7 @@ static int search_segments(int64_t Q, int64_t G, int k, int segments, int BM, in
   }
   S = std::min<int64_t>(S, tiles_n);
   S = std::min<int64_t>(S, kMergeMaxLists);
-  S = std::min<int64_t>(S, 8192 / k);
+  S = std::min<int64_t>(S, kMergeMaxEntries / k);
   return (int)std::max<int64_t>(S, 1);
 }
 

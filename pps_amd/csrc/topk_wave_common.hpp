@@ -1,4 +1,4 @@
-// Wave-level pieces of the streaming stable top-k (rank.hip's topk_wave_kernel,
+// Wave-level pieces of the streaming stable top-k (topk.hip's topk_wave_kernel,
 // search_h2.hip's filter epilogue): the order-preserving packing of a distance
 // and the bisection select / cut of a wave's candidate buffer.
 #pragma once
@@ -18,7 +18,7 @@ __device__ inline float key_float(uint32_t k) {
   return __uint_as_float(u);
 }
 
-constexpr int kTkwMaxK = 256;
+// (the largest k, kTkwMaxK: retrieval.hpp)
 constexpr int kTkwSlack = 64;               // a streaming cut keeps k .. k + slack entries
 
 __device__ inline void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }

@@ -853,42 +853,6 @@ def cmc_finalize(pos_total, hist, topk, first_match_break):
     return ret, valid
 
 
-def collect_positives(dist, qid, qcam, gid, gcam, g_offset, Pmax):
-    Q, G = dist.shape
-    pos_d = torch.empty((Q, Pmax), dtype=torch.float32, device=dist.device)
-    pos_idx = torch.empty((Q, Pmax), dtype=torch.int32, device=dist.device)
-    pos_cnt = torch.empty((Q,), dtype=torch.int32, device=dist.device)
-    call('pps_collect_positives', _dev_rows(dist, 'dist'), Q, G, _ld(dist),
-         _dev(qid, 'qid', torch.int32), _dev(qcam, 'qcam', torch.int32),
-         _dev(gid, 'gid', torch.int32), _dev(gcam, 'gcam', torch.int32), int(g_offset),
-         Pmax, pos_d.data_ptr(), pos_idx.data_ptr(), pos_cnt.data_ptr(), _stream())
-    return pos_d, pos_idx, pos_cnt
-
-
-def rank_counts(dist, qid, qcam, gid, gcam, g_offset, pos_d, pos_idx, pos_cnt,
-                hist=None, before=None):
-    """pos_* are [R,Q,Pmax] / [R,Q] merged lists.  hist/before accumulate."""
-    Q, G = dist.shape
-    R, _, Pmax = pos_d.shape
-    Ptot = R * Pmax
-    dev = dist.device
-    sorted_d = torch.empty((Q, Ptot), dtype=torch.float32, device=dev)
-    sorted_idx = torch.empty((Q, Ptot), dtype=torch.int32, device=dev)
-    pos_total = torch.empty((Q,), dtype=torch.int32, device=dev)
-    if hist is None:
-        hist = torch.zeros((Q, Ptot), dtype=torch.int32, device=dev)
-    if before is None:
-        before = torch.zeros((Q,), dtype=torch.int32, device=dev)
-    call('pps_rank_counts', _dev_rows(dist, 'dist'), Q, G, _ld(dist),
-         _dev(qid, 'qid', torch.int32), _dev(qcam, 'qcam', torch.int32),
-         _dev(gid, 'gid', torch.int32), _dev(gcam, 'gcam', torch.int32), int(g_offset),
-         R, Pmax, _dev(pos_d, 'pos_d'), _dev(pos_idx, 'pos_idx', torch.int32),
-         _dev(pos_cnt, 'pos_cnt', torch.int32), sorted_d.data_ptr(),
-         sorted_idx.data_ptr(), pos_total.data_ptr(), _dev(hist, 'hist', torch.int32),
-         _dev(before, 'before', torch.int32), _stream())
-    return sorted_d, sorted_idx, pos_total, hist, before
-
-
 def ap_finalize(sorted_d, pos_total, hist, before):
     Q, Ptot = sorted_d.shape
     dev = sorted_d.device

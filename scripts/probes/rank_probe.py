@@ -1,5 +1,6 @@
-"""Probe: rank_count_stream variants on the Market-size distance matrix.
-  PPS_LIB_PATH=_variants/libpps_hip_X.so python scripts/rank_probe.py"""
+"""Probe: rank_count_stream's time and bandwidth on the Market-size distance
+matrix, for the built library or another build of it.
+  [PPS_LIB_PATH=path/to/libpps_hip.so] python scripts/probes/rank_probe.py"""
 import os
 import sys
 
