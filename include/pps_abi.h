@@ -501,6 +501,46 @@ int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, c
                              float* vals, int32_t* idx,
                              const int32_t* q_group, const int32_t* g_group, void* stream);
 
+/* Count-based mAP without the [Q, G] matrix: the two steps of the rank
+ * evaluation above that read distances, computing them on the fly from the
+ * f16x2 planes.  Operands (q2t .. D, metric) and their checks are
+ * pps_search_h2_tiled's; every distance has the bits pps_distmat_h2_tiled
+ * would write, so all outputs equal those of pps_collect_matches /
+ * pps_rank_count_stream on that matrix exactly.  pps_rank_prepare and
+ * pps_ap_finalize run unchanged between and after them.
+ *  - pps_collect_matches_h2: pps_collect_matches with the planes in place of
+ *    dist (members / q_beg / q_end / qcam / gcam / g_offset / Pmax / Jmax and
+ *    all six outputs as there; entries in member order).
+ *  - pps_rank_count_h2_tiled: pps_rank_count_stream's additive hist [Q][Ptot] /
+ *    before [Q] for this gallery (shard, segment) [g_offset, g_offset + G):
+ *    ADDED into the caller's buffers (zeroed, or carrying earlier segments'
+ *    counts); rows with pos_total == 0 are skipped; Q == 0 or G == 0 adds
+ *    nothing.  The junk lists are this gallery's, from pps_collect_matches_h2.
+ *    Ptot <= pps_rank_count_h2_max_p() (1024), else PPS_ERR_CAPACITY: longer
+ *    lists take the materialised path.  segments / tile: as in
+ *    pps_search_h2_tiled (segments clamped to the gallery's tile count only).
+ *    workspace: a device buffer of pps_rank_count_h2_workspace_bytes(Q, G,
+ *    Ptot, segments) bytes (host function, non-decreasing in G, -1 on bad
+ *    arguments) -- 0 today, the counts leave the kernel as atomics, and a
+ *    null pointer is then accepted. */
+int pps_rank_count_h2_max_p(void);
+int64_t pps_rank_count_h2_workspace_bytes(int64_t Q, int64_t G, int Ptot, int segments);
+int pps_collect_matches_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                           const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                           int D, int metric, const int32_t* qcam, const int32_t* gcam,
+                           const int32_t* members, const int32_t* q_beg, const int32_t* q_end,
+                           int64_t g_offset, int Pmax, float* pos_d, int32_t* pos_idx,
+                           int32_t* pos_cnt, int Jmax, float* junk_d, int32_t* junk_idx,
+                           int32_t* junk_cnt, void* stream);
+int pps_rank_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                            int D, int metric, int64_t g_offset, int Ptot,
+                            const float* sorted_d, const int32_t* sorted_idx,
+                            const int32_t* pos_total, int Jmax, const float* junk_d,
+                            const int32_t* junk_idx, const int32_t* junk_cnt, int segments,
+                            int tile, void* workspace, int64_t ws_bytes, int32_t* hist,
+                            int32_t* before, void* stream);
+
 /* k-reciprocal re-ranking (reid_dataset_evaluator.py:442-519): out [Q][G] =
  * re_ranking(q_g, q_q, g_g, k1, k2, lambda) with the reference's float32
  * operand order for V, V_qe and the Jaccard sums; ties in the initial rank use

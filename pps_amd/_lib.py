@@ -96,6 +96,12 @@ SIGNATURES = {
     'pps_search_h2_tiled_excl': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
                                  c_int, c_int, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
                                  c_ptr, c_ptr],
+    'pps_collect_matches_h2': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                               c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr,
+                               c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
+    'pps_rank_count_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                                c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
+                                c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],
@@ -188,6 +194,8 @@ EXTRA = {
     'pps_search_max_k': ([], ctypes.c_int),
     'pps_search_h2_num_tiles': ([], ctypes.c_int),
     'pps_search_h2_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
+    'pps_rank_count_h2_max_p': ([], ctypes.c_int),
+    'pps_rank_count_h2_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
     'pps_rank_cells': ([], ctypes.c_int),
     'pps_argsort_rows_cap': ([], ctypes.c_int),
     'pps_stem_k': ([], ctypes.c_int),

@@ -26,9 +26,42 @@ constexpr int kRankStreamChunk = 256 * 4 * kRankStreamU;
 // 16 B per merged positive, 128 KiB at the cap
 constexpr int kRankMergeCap = 8192;
 static_assert(16 * kRankMergeCap <= kLdsBytesGfx950, "rank_prepare LDS exceeds the CU's LDS");
+// fused f16x2 kernels (search_h2.hip, rank_h2.hip): tile ids 0 = default (1),
+// 1 = 256 x 256 two-stage, 2 = 192 x 192 three-stage
+constexpr int kSearchNumTiles = 3;
+constexpr int kSearchSlots = 256;    // workgroups launched at most: one per CU (LDS-bound residency)
+// rank_count_h2: longest merged positive list (Ptot).  The kernel bins a pass
+// of columns against the list with one ballot per positive; beyond the cap
+// rank_count_stream's binary search on the matrix is the right algorithm
+constexpr int kRankH2MaxP = 1024;
 // sgs_groups keeps two int32 bounds per gallery identity in LDS (plus G / 4 bytes)
 constexpr int kSgsMaxIds = 16384;
 static_assert(8 * kSgsMaxIds <= kLdsBytesGfx950, "sgs_groups LDS exceeds the CU's LDS");
+
+// ---- host plan of the fused f16x2 kernels (search_h2.hip, rank_h2.hip) ----------
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline void search_tile_shape(int tile, int& BM, int& BN) {
+  if (tile == 2) { BM = 192; BN = 192; } else { BM = 256; BN = 256; }
+}
+// Gallery segments of a (query panel, gallery segment) work list before they
+// are rounded to whole tiles per segment: the request, or (0 = auto) the count
+// at which panels x S fills the CUs once or twice, whichever leaves the
+// smaller idle tail; never more than the gallery's tiles.  Non-decreasing in G.
+inline int64_t fused_segments(int64_t Q, int64_t G, int segments, int BM, int BN) {
+  const int64_t panels = cdiv(Q, BM) > 1 ? cdiv(Q, BM) : 1;
+  const int64_t tiles_n = cdiv(G, BN) > 1 ? cdiv(G, BN) : 1;
+  int64_t S = segments;
+  if (S <= 0) {
+    const int64_t s1 = kSearchSlots / panels > 1 ? kSearchSlots / panels : 1;
+    const int64_t s2 = 2 * kSearchSlots / panels > 1 ? 2 * kSearchSlots / panels : 1;
+    auto fill = [&](int64_t s) {
+      const int64_t items = panels * s;
+      return (double)items / (double)(cdiv(items, kSearchSlots) * kSearchSlots);
+    };
+    S = fill(s2) > fill(s1) ? s2 : s1;
+  }
+  return S < tiles_n ? S : tiles_n;
+}
 
 // ---- evaluation counts (eval_counts.hip) ----------------------------------------
 int collect_matches(const float* dist, int64_t Q, int64_t ldd, const int32_t* qcam,

@@ -42,8 +42,7 @@
 
 namespace pps {
 
-constexpr int kSearchNumTiles = 3;   // 0 = default (1), 1 = 256 x 256 two-stage, 2 = 192 x 192 three-stage
-constexpr int kSearchSlots = 256;    // workgroups launched at most: one per CU (LDS-bound residency)
+// tile ids (kSearchNumTiles) and the launch width (kSearchSlots): retrieval.hpp
 constexpr int kSearchMaxBM = 256;    // rows of a slot's buffer set
 constexpr int kSearchInflow = 256;   // most columns a row can receive between two cut checks
 // entries of one row's candidate buffer: what a cut keeps + one pass's inflow
@@ -244,31 +243,14 @@ __global__ void search_fill_pad_kernel(float* vals, int32_t* idx, int64_t n) {
 }
 
 // ---- host plan ---------------------------------------------------------------
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
-static void search_tile_shape(int tile, int& BM, int& BN) {
-  if (tile == 2) { BM = 192; BN = 192; } else { BM = 256; BN = 256; }
-}
-
-// Segment count before it is rounded to whole tiles per segment: the request
-// (0 = auto: panels x S fills the CUs once or twice, whichever leaves the
-// smaller idle tail) under the clamps -- the segment's tile count, and
-// topk_merge's kMergeMaxLists lists and kMergeMaxEntries merged entries.
-// Non-decreasing in G.
+// Segment count before it is rounded to whole tiles per segment:
+// fused_segments (the request, 0 = auto, under the segment's tile count) under
+// topk_merge's clamps -- kMergeMaxLists lists and kMergeMaxEntries merged
+// entries.  Non-decreasing in G.
 static int search_segments(int64_t Q, int64_t G, int k, int segments, int BM, int BN) {
-  const int64_t panels = std::max<int64_t>(cdiv(Q, BM), 1), tiles_n = std::max<int64_t>(cdiv(G, BN), 1);
-  int64_t S = segments;
-  if (S <= 0) {
-    const int64_t s1 = std::max<int64_t>(kSearchSlots / panels, 1);
-    const int64_t s2 = std::max<int64_t>(2 * kSearchSlots / panels, 1);
-    auto fill = [&](int64_t s) {
-      const int64_t items = panels * s;
-      return (double)items / (double)(cdiv(items, kSearchSlots) * kSearchSlots);
-    };
-    S = fill(s2) > fill(s1) ? s2 : s1;
-  }
-  S = std::min<int64_t>(S, tiles_n);
+  int64_t S = fused_segments(Q, G, segments, BM, BN);
   S = std::min<int64_t>(S, kMergeMaxLists);
   S = std::min<int64_t>(S, kMergeMaxEntries / k);
   return (int)std::max<int64_t>(S, 1);

@@ -176,6 +176,40 @@ class HipBackend(object):
     def finalize(sorted_d, pos_total, hist, before):
         return ops.ap_finalize(sorted_d, pos_total, hist, before)
 
+    @classmethod
+    def fused_operands(cls, q, g, ptot):
+        """(queries' f16x2 split, h2 GalleryIndex of this shard) for
+        collect_fused / counts_fused, or None where the matrix-free kernels do
+        not apply and run() builds the block after all: another distance
+        arithmetic than 'h2', D % 32 != 0, merged positive lists wider than
+        the count kernel's cap."""
+        if (cls.distmat_math or ops.dist_math()) != 'h2':
+            return None
+        if q.shape[1] % 32 != 0 or ptot > ops.rank_count_h2_max_p():
+            return None
+        if isinstance(g, ops.GalleryIndex):
+            if g.h2 is None:
+                return None
+            index = g
+        else:
+            index = ops.GalleryIndex(g if g.is_contiguous() else g.contiguous(), math='h2')
+        return ops.split_h2_tiled(q if q.is_contiguous() else q.contiguous()), index
+
+    @staticmethod
+    def collect_fused(operands, ev, state, pmax):
+        """collect() without the block: the matches' distances computed from
+        the operands (ops.collect_matches_h2), the same bits."""
+        q_split, index = operands
+        return ops.collect_matches_h2(q_split, index, state, ev.metric, ev.g_offset, pmax)
+
+    @staticmethod
+    def counts_fused(operands, ev, state, pos_d, pos_idx, pos_cnt, local):
+        """counts() without the block (ops.rank_count_h2), the same counts."""
+        q_split, index = operands
+        sp = ops.rank_prepare(pos_d, pos_idx, pos_cnt)
+        hist, before = ops.rank_count_h2(q_split, index, ev.g_offset, sp, local, ev.metric)
+        return sp.sorted_d, sp.sorted_idx, sp.pos_total, hist, before
+
     @staticmethod
     def topk(dist, k):
         return ops.topk(dist, k)
@@ -278,27 +312,52 @@ class ShardedEvaluator(object):
             return [t[None] for t in ts]
         return [all_gather_rows(t[None], [1] * self.world) for t in ts]
 
-    def run(self, q_local, g_local, timed=False, dist=None, keep_dist=False):
+    def run(self, q_local, g_local, timed=False, dist=None, keep_dist=False, fused=False):
+        """fused=True (no `dist` given, a backend with collect_fused and
+        counts_fused): this shard's [Q, G] block is never built -- the matches'
+        distances and the rank counts come from kernels that compute the f16x2
+        distances on the fly (ops.collect_matches_h2 / ops.rank_count_h2), the
+        same bits and counts, so every result equals run()'s; the list
+        all-gather, the merge, the all-reduces and the finalisation are the
+        same code.  A backend without the two methods (the CPU oracle backend)
+        and the cases HipBackend.fused_operands names take the matrix path.
+        There is then no block to keep: keep_dist=True with fused=True is an
+        error.  Off by default (what it measures)."""
+        if fused and keep_dist:
+            raise RuntimeError('ShardedEvaluator.run: keep_dist=True needs the distance block, '
+                               'which fused=True never builds')
         be = self.backend
         use_ev = timed and be.device == 'cuda'
         if use_ev:
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             evs[0].record()
+        operands = None
         if dist is None:
             q_all = all_gather_rows(q_local, self.q_sizes)
             if use_ev:
                 evs[1].record()
-            dist = be.distmat(q_all, g_local, self.metric)
+            if fused and hasattr(be, 'collect_fused') and hasattr(be, 'counts_fused'):
+                operands = be.fused_operands(q_all, g_local, self.world * self.pmax)
+            if operands is None:
+                dist = be.distmat(q_all, g_local, self.metric)
         elif use_ev:
             evs[1].record()
         if use_ev:
             evs[2].record()
         if self._state is None:
             self._state = be.prepare(self)
-        pos_d, pos_idx, pos_cnt, local = be.collect(dist, self, self._state, self.pmax)
+        if operands is not None:
+            pos_d, pos_idx, pos_cnt, local = be.collect_fused(operands, self, self._state,
+                                                              self.pmax)
+        else:
+            pos_d, pos_idx, pos_cnt, local = be.collect(dist, self, self._state, self.pmax)
         pos_d, pos_idx, pos_cnt = self._gather_lists(pos_d, pos_idx, pos_cnt)
-        sorted_d, _, pos_total, hist, before = be.counts(
-            dist, self, self._state, pos_d, pos_idx, pos_cnt, local)
+        if operands is not None:
+            sorted_d, _, pos_total, hist, before = be.counts_fused(
+                operands, self, self._state, pos_d, pos_idx, pos_cnt, local)
+        else:
+            sorted_d, _, pos_total, hist, before = be.counts(
+                dist, self, self._state, pos_d, pos_idx, pos_cnt, local)
         self._all_reduce(hist)
         self._all_reduce(before)
         ap, valid, first = be.finalize(sorted_d, pos_total, hist, before)

@@ -670,20 +670,7 @@ def search(q, gallery, k, metric='euclidean', segments=0, tile=0, workspace=None
     the general kernel's below the diagonal).
     The fallback cases above then run compute_dist + topk_excluding, which
     materialises the matrix, a masked copy of it and a byte mask."""
-    if isinstance(gallery, GalleryIndex):
-        parts = [gallery]
-    elif isinstance(gallery, torch.Tensor):
-        g = gallery
-        h2ok = g.dim() == 2 and g.shape[1] % 32 == 0
-        parts = [GalleryIndex(g if g.is_contiguous() or not h2ok else g.contiguous(),
-                              math='h2' if h2ok else None)]
-    else:
-        parts = list(gallery)
-        if not parts or not all(isinstance(p, GalleryIndex) for p in parts):
-            raise RuntimeError('search: gallery must be a tensor, a GalleryIndex or a '
-                               'non-empty sequence of GalleryIndex')
-    if q.dim() != 2 or any(p.shape[1] != q.shape[1] for p in parts):
-        raise RuntimeError('search expects [Q, D] queries and [G, D] galleries')
+    parts = _gallery_parts('search', q, gallery)
     k = int(k)
     if k < 1:
         raise RuntimeError('search: k must be >= 1')
@@ -864,6 +851,231 @@ def ap_finalize(sorted_d, pos_total, hist, before):
          _dev(before, 'before', torch.int32), ap.data_ptr(), valid.data_ptr(),
          first.data_ptr(), _stream())
     return ap, valid, first
+
+
+def rank_count_h2_max_p():
+    """Longest merged positive list (sorted_d's width) the fused count kernel
+    takes (pps_rank_count_h2_max_p)."""
+    return int(_lib.lib().pps_rank_count_h2_max_p())
+
+
+def rank_count_h2_workspace_bytes(Q, G, Ptot, segments=0):
+    """Bytes of device workspace one rank_count_h2 call needs
+    (pps_rank_count_h2_workspace_bytes; host arithmetic only, non-decreasing in
+    G).  0 today: the kernel's counts leave it as atomics."""
+    n = int(_lib.lib().pps_rank_count_h2_workspace_bytes(int(Q), int(G), int(Ptot),
+                                                         int(segments)))
+    if n < 0:
+        raise RuntimeError('rank_count_h2_workspace_bytes: bad arguments Q=%r G=%r Ptot=%r '
+                           'segments=%r (1 <= Ptot <= %d)'
+                           % (Q, G, Ptot, segments, rank_count_h2_max_p()))
+    return n
+
+
+def _h2_operands(fn, q_split, index):
+    """The ten leading arguments of the fused h2 entry points (queries' and
+    gallery's planes, norms, scales, shapes)."""
+    if not isinstance(index, GalleryIndex) or index.h2 is None:
+        raise RuntimeError('%s: the gallery must be a GalleryIndex holding an h2 split' % fn)
+    q2, qrs, qsq = q_split
+    g2, grs, gsq = index.h2
+    Q, G, D = qsq.shape[0], index.shape[0], index.shape[1]
+    if q2.dim() != 3 or q2.shape[2] != D or q2.shape[1] != (Q + 15) // 16 * 16:
+        raise RuntimeError('%s: q_split %s does not fit %d queries of width %d'
+                           % (fn, tuple(q2.shape), Q, D))
+    return (_dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'), _dev(qrs, 'qrs'),
+            _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G, D)
+
+
+def collect_matches_h2(q_split, index, match_index, metric='euclidean', g_offset=0, pmax=None):
+    """collect_matches without the matrix (pps_collect_matches_h2): q_split =
+    split_h2_tiled(queries), index an h2 GalleryIndex, match_index the
+    MatchIndex of the same queries and gallery rows.  The same tuple, each
+    distance with the bits compute_dist(q, index, math='h2') holds at that
+    cell."""
+    args = _h2_operands('collect_matches_h2', q_split, index)
+    Q, G = args[1], args[7]
+    if (Q, G) != (match_index.Q, match_index.G):
+        raise RuntimeError('operands (%d, %d) do not match the index (%d, %d)'
+                           % (Q, G, match_index.Q, match_index.G))
+    pmax = pmax or match_index.capacity
+    jmax = match_index.capacity
+    dev = q_split[0].device
+    pos_d = torch.empty((Q, pmax), dtype=torch.float32, device=dev)
+    pos_idx = torch.empty((Q, pmax), dtype=torch.int32, device=dev)
+    pos_cnt = torch.empty((Q,), dtype=torch.int32, device=dev)
+    junk_d = torch.empty((Q, jmax), dtype=torch.float32, device=dev)
+    junk_idx = torch.empty((Q, jmax), dtype=torch.int32, device=dev)
+    junk_cnt = torch.empty((Q,), dtype=torch.int32, device=dev)
+    mi = match_index
+    call('pps_collect_matches_h2', *(args + (
+        METRICS[metric], _dev(mi.qcam, 'qcam', torch.int32), _dev(mi.gcam, 'gcam', torch.int32),
+        _dev(mi.members, 'members', torch.int32), _dev(mi.q_beg, 'q_beg', torch.int32),
+        _dev(mi.q_end, 'q_end', torch.int32), int(g_offset), pmax, pos_d.data_ptr(),
+        pos_idx.data_ptr(), pos_cnt.data_ptr(), jmax, junk_d.data_ptr(), junk_idx.data_ptr(),
+        junk_cnt.data_ptr(), _stream())))
+    return pos_d, pos_idx, pos_cnt, (junk_d, junk_idx, junk_cnt)
+
+
+def rank_count_h2(q_split, index, g_offset, sp, junk, metric='euclidean', hist=None,
+                  before=None, segments=0, tile=0, workspace=None):
+    """rank_count_stream without the matrix (pps_rank_count_h2_tiled): the
+    additive (hist, before) counts of this gallery (shard, segment) against
+    the SortedPositives sp, distances computed on the fly from q_split and the
+    h2 GalleryIndex; junk = this gallery's junk lists from collect_matches_h2.
+    hist / before accumulate when given.  sp's width must not exceed
+    rank_count_h2_max_p().  segments / tile: as in search (same counts)."""
+    args = _h2_operands('rank_count_h2', q_split, index)
+    Q, G = args[1], args[7]
+    Ptot = sp.sorted_d.shape[1]
+    junk_d, junk_idx, junk_cnt = junk
+    dev = q_split[0].device
+    if hist is None:
+        hist = torch.zeros((Q, Ptot), dtype=torch.int32, device=dev)
+    if before is None:
+        before = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    if tuple(hist.shape) != (Q, Ptot) or tuple(before.shape) != (Q,):
+        raise RuntimeError('rank_count_h2: hist must be [%d, %d] and before [%d]' % (Q, Ptot, Q))
+    ws_ptr = ws_bytes = 0
+    if workspace is not None:
+        if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
+                not workspace.is_contiguous()):
+            raise RuntimeError('rank_count_h2: workspace must be a contiguous device tensor')
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    call('pps_rank_count_h2_tiled', *(args + (
+        METRICS[metric], int(g_offset), Ptot, _dev(sp.sorted_d, 'sorted_d'),
+        _dev(sp.sorted_idx, 'sorted_idx', torch.int32),
+        _dev(sp.pos_total, 'pos_total', torch.int32), junk_d.shape[1], _dev(junk_d, 'junk_d'),
+        _dev(junk_idx, 'junk_idx', torch.int32), _dev(junk_cnt, 'junk_cnt', torch.int32),
+        int(segments), int(tile), ws_ptr, ws_bytes, _dev(hist, 'hist', torch.int32),
+        _dev(before, 'before', torch.int32), _stream())))
+    return hist, before
+
+
+def _gallery_parts(fn, q, gallery):
+    """gallery as search takes it -> the list of GalleryIndex segments."""
+    if isinstance(gallery, GalleryIndex):
+        parts = [gallery]
+    elif isinstance(gallery, torch.Tensor):
+        g = gallery
+        h2ok = g.dim() == 2 and g.shape[1] % 32 == 0
+        parts = [GalleryIndex(g if g.is_contiguous() or not h2ok else g.contiguous(),
+                              math='h2' if h2ok else None)]
+    else:
+        parts = list(gallery)
+        if not parts or not all(isinstance(p, GalleryIndex) for p in parts):
+            raise RuntimeError('%s: gallery must be a tensor, a GalleryIndex or a '
+                               'non-empty sequence of GalleryIndex' % fn)
+    if q.dim() != 2 or any(p.shape[1] != q.shape[1] for p in parts):
+        raise RuntimeError('%s expects [Q, D] queries and [G, D] galleries' % fn)
+    return parts
+
+
+RANK_FUSED_MAX_SEGMENTS = 64   # pps_rank_prepare merges at most 64 lists per query
+
+
+def rank_eval_fused(q, gallery, qid, qcam, gid, gcam, metric='euclidean', segments=0, tile=0,
+                    match_index=None):
+    """Per-query (ap float64, valid int32, first_rank int32) -- what
+    reid_dataset_evaluator.rank_eval returns on compute_dist(q, gallery,
+    math='h2'), bit for bit -- without the [Q, G] matrix: the true matches'
+    distances from pps_collect_matches_h2, pps_rank_prepare, the counts from
+    the fused distance + count kernel pps_rank_count_h2_tiled, pps_ap_finalize.
+    mAP = ap[valid].mean(); first_rank gives the first-match (Market) CMC.
+
+    gallery: what search takes -- a [G, D] tensor (indexed on the fly), a
+    GalleryIndex, or a sequence of GalleryIndex objects holding consecutive row
+    segments of one logical gallery (GalleryIndex.split).  qid / qcam [Q] and
+    gid / gcam [G] are host metadata of the whole logical gallery.  The queries
+    are split once.  For a sequence, every segment gets its own MatchIndex and
+    one collect with the segment's start as g_offset; pps_rank_prepare merges
+    the stacked lists in one call -- more than 64 segments is an error, not
+    merged in rounds -- and the merged lists are trimmed to the longest true
+    list the ids allow (max_positives); then one count per segment adds into
+    the same hist / before.  segments / tile: the count kernel's, as in search.
+    match_index: the segments' MatchIndex objects (one, or a sequence in segment
+    order) built earlier from the same ids, as rank_eval's `index`; None builds
+    them (host, O(G log G)).
+
+    A segment falls back to the materialised path -- compute_dist, then
+    collect_matches / rank_count_stream on ITS [Q, rows] block, which is built
+    for the collect and again for the count when there are several segments
+    (one block lives at a time) -- when the fused kernels do not apply: an
+    index holding an x3 split, D % 32 != 0, non-contiguous queries (copied to
+    whole rows), or, for the count only, merged lists wider than
+    rank_count_h2_max_p().
+
+    Measured against compute_dist + rank_eval it is
+    the slower path: 2.5 against 1.1 ms at the Market shape, 32.6 against 15.8
+    ms at a 10,000 x 125,000 shard (1.9 / 30.9 ms on clustered features), the
+    count kernel alone twice the plain distance GEMM.  The gain is memory -- a
+    0.19 GB peak where that path holds the 5.1 GB block -- and a path for a
+    gallery split over several indexes, which one compute_dist call cannot
+    take."""
+    parts = _gallery_parts('rank_eval_fused', q, gallery)
+    if len(parts) > RANK_FUSED_MAX_SEGMENTS:
+        raise RuntimeError('rank_eval_fused: %d gallery segments, pps_rank_prepare merges at '
+                           'most %d lists per query' % (len(parts), RANK_FUSED_MAX_SEGMENTS))
+    qid, qcam, gid, gcam = (np.asarray(a).reshape(-1) for a in (qid, qcam, gid, gcam))
+    Q, D = q.shape
+    starts = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+    if len(qid) != Q or len(qcam) != Q or len(gid) != starts[-1] or len(gcam) != starts[-1]:
+        raise RuntimeError('rank_eval_fused: %d queries / %d gallery rows, ids and cams of '
+                           '%d / %d / %d / %d' % (Q, starts[-1], len(qid), len(qcam), len(gid),
+                                                  len(gcam)))
+    if starts[-1] >= 2 ** 31:
+        raise RuntimeError('rank_eval_fused: gallery indices must fit int32')
+    dev = q.device
+    if Q == 0:
+        return (torch.empty((0,), dtype=torch.float64, device=dev),
+                torch.empty((0,), dtype=torch.int32, device=dev),
+                torch.empty((0,), dtype=torch.int32, device=dev))
+    q_split = None
+    if D % 32 == 0 and q.is_contiguous() and any(p.h2 is not None for p in parts):
+        q_split = split_h2_tiled(q)   # once, as compute_dist splits them
+    qc = q if q.is_contiguous() else q.contiguous()   # compute_dist takes whole rows
+    fusable = [q_split is not None and p.h2 is not None for p in parts]
+    block = lambda p: compute_dist(qc, p, metric=metric, pad_rows=True)
+    keep = len(parts) == 1   # a lone segment's block serves the collect and the count
+    if match_index is None:
+        mis = [MatchIndex(qid, qcam, gid[int(a):int(b)], gcam[int(a):int(b)], dev)
+               for a, b in zip(starts[:-1], starts[1:])]
+    else:
+        mis = [match_index] if isinstance(match_index, MatchIndex) else list(match_index)
+        if [(m.Q, m.G) for m in mis] != [(Q, p.shape[0]) for p in parts]:
+            raise RuntimeError('rank_eval_fused: match_index does not fit the queries and '
+                               'the gallery segments')
+    pmax = max(mi.capacity for mi in mis)
+    lists, junks, kept = [], [], None
+    for p, mi, a, f in zip(parts, mis, starts[:-1], fusable):
+        if f:
+            pd, pi, pc, junk = collect_matches_h2(q_split, p, mi, metric, int(a), pmax)
+        else:
+            dist = block(p)
+            pd, pi, pc, junk = collect_matches(dist, mi, int(a), pmax)
+            kept = dist if keep else None
+            del dist
+        lists.append((pd, pi, pc))
+        junks.append(junk)
+    sp = rank_prepare(*(torch.stack([l[i] for l in lists]) for i in range(3)))
+    del lists
+    # one list is as wide as the identity's rows; R stacked ones are R times that
+    ptrue = max(1, max_positives(qid, qcam, gid, gcam)) if len(parts) > 1 else pmax
+    if ptrue < sp.sorted_d.shape[1]:   # the tail is padding for every query
+        sp = SortedPositives(sp.sorted_d[:, :ptrue].contiguous(),
+                             sp.sorted_idx[:, :ptrue].contiguous(), sp.pos_total, sp.cells)
+    Ptot = sp.sorted_d.shape[1]
+    hist = torch.zeros((Q, Ptot), dtype=torch.int32, device=dev)
+    before = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    fits = Ptot <= rank_count_h2_max_p()
+    for p, a, f, junk in zip(parts, starts[:-1], fusable, junks):
+        if f and fits:
+            rank_count_h2(q_split, p, int(a), sp, junk, metric, hist, before, segments, tile)
+        else:
+            dist = kept if kept is not None else block(p)
+            rank_count_stream(dist, int(a), sp, junk, hist, before)
+            del dist
+    return ap_finalize(sp.sorted_d, sp.pos_total, hist, before)
 
 
 def re_ranking(q_g, q_q, g_g, k1=20, k2=6, lambda_value=0.3, symmetric=None, whole=False):

@@ -214,6 +214,51 @@ def cmc_from_search(query_feats, gallery, query_ids=None, gallery_ids=None, quer
     return ret, valid.astype(np.float64)
 
 
+def rank_eval_from_features(query_feats, gallery, query_ids, gallery_ids, query_cams,
+                            gallery_cams, metric='euclidean'):
+    """rank_eval without a distance matrix: per-query (ap float64, valid int32,
+    first_rank int32) straight from the features (ops.rank_eval_fused: the
+    matches' distances and the rank counts come from kernels that compute the
+    f16x2 distances on the fly).  Equal, bit for bit, to rank_eval on
+    ops.compute_dist(query_feats, gallery, math='h2').  gallery: a [G, D]
+    array or tensor, an ops.GalleryIndex, or a sequence of them (a gallery
+    split over several indexes, ops.GalleryIndex.split).  ops.rank_eval_fused
+    lists the cases that DO materialise a block (an x3 index, D % 32 != 0,
+    strided queries, positive lists beyond the count kernel's cap)."""
+    if not isinstance(gallery, (ops.GalleryIndex, list, tuple)):
+        gallery = _to_dev(gallery)
+    return ops.rank_eval_fused(_to_dev(query_feats), gallery, _host_ids(query_ids),
+                               _host_ids(query_cams), _host_ids(gallery_ids),
+                               _host_ids(gallery_cams), metric=metric)
+
+
+def mean_ap_from_features(query_feats, gallery, query_ids=None, gallery_ids=None,
+                          query_cams=None, gallery_cams=None, average=True,
+                          metric='euclidean'):
+    """mean_ap (:366-439) without a distance matrix (rank_eval_from_features):
+    the same outputs and the same `average` argument."""
+    ap, valid, _ = rank_eval_from_features(query_feats, gallery, query_ids, gallery_ids,
+                                           query_cams, gallery_cams, metric)
+    ap, valid = _np(ap), _np(valid).astype(np.float64)
+    if average:
+        return float(np.sum(ap)) / np.sum(valid)
+    return ap, valid
+
+
+def evaluate_from_features(query_feats, gallery, query_ids, gallery_ids, query_cams,
+                           gallery_cams, metric='euclidean', topk=10):
+    """(mAP, cmc[topk]) of the Market protocol -- mean_ap and
+    cmc(first_match_break=True) -- without a distance matrix: one
+    rank_eval_from_features pass, scored by scores_from_ranks like evaluate().
+    The fractional CMC (first_match_break=False) and separate_camera_set need
+    pps_cmc_counts' key-based bins, which have no matrix-free kernel: they are
+    out of scope here, use cmc on a matrix (or cmc_from_search for the
+    separate-camera first-match CMC)."""
+    ap, valid, first = rank_eval_from_features(query_feats, gallery, query_ids, gallery_ids,
+                                               query_cams, gallery_cams, metric)
+    return scores_from_ranks(ap, valid, first, topk=topk)
+
+
 SGS_MAX_IDS = 16384   # pps_sgs_keys / pps_sgs_groups (include/pps_abi.h)
 
 

@@ -36,8 +36,24 @@ peaks; and, at the shard shape, the matrix-free first-match CMC
 first_match_break=True) on the materialised matrix: wall clock around a
 device synchronize (both have host parts), peaks, equality of the curves.
 
+--rank replaces them by the matrix-free mAP legs at the same two shapes and
+labels:
+
+  A  ops.compute_dist into a preallocated buffer, then rank_eval on it
+  B  ops.rank_eval_fused (no [Q, G] matrix)
+
+alternating under the same repetition scheme, on two kinds of features --
+normalised Gaussians unrelated to the labels (every column ranks before some
+last positive: the count kernels' worst case) and identity centroids + noise
+(_clustered_feats: a few percent of the columns do) -- both with the MatchIndex
+built once beforehand, B on the count kernel's tile and segment count one timed
+sweep picks; peaks; each path's kernels alone (the distance GEMM,
+collect_matches, rank_count_stream; the query split, collect_matches_h2 = the
+pair-distance kernel, rank_count_h2 = the fused count kernel); and an error
+unless B's per-query ap (float64 bits), valid and first_rank equal A's.
+
   python scripts/bench_search.py [--reps 5] [--shapes market,shard] [--segmented]
-                                 [--exclude [--parent-lib PATH]]
+                                 [--exclude [--parent-lib PATH]] [--rank]
 """
 import argparse
 import ctypes
@@ -347,18 +363,146 @@ def bench_exclude(name, Q, G, D, k, reps, ops, parent_lib=None, cmc=False):
     return res
 
 
+def _clustered_feats(cent, ids, gen, z=2.5):
+    """Identity centroid (cent [ids, D], shared by queries and gallery) + noise,
+    normalised.  The noise level puts a same-id pair z standard deviations (of a
+    different-id pair's squared distance, 2 / sqrt(D)) closer than a
+    different-id pair: positives rank early but not first, and the columns at
+    or before a query's LAST positive -- what the count kernels bin -- are a
+    fraction of the gallery, not all of it."""
+    D = cent.shape[1]
+    ids = torch.from_numpy(np.asarray(ids)).cuda()
+    sigma = max(D ** 0.5 / z - 1.0, 0.0) ** 0.5
+    x = cent[ids] + sigma * torch.randn(len(ids), D, generator=gen, device='cuda')
+    x /= x.norm(dim=1, keepdim=True)
+    return x
+
+
+def bench_rank(name, Q, G, D, reps, ops, features='gaussian'):
+    """A = compute_dist into a preallocated buffer + rank_eval on it, B =
+    rank_eval_fused (no [Q, G] matrix); both get the MatchIndex built once
+    (host), so the timed part is device work and the wrappers between the
+    launches.  Also each path's kernels alone.  Raises unless B's (ap, valid,
+    first_rank) equal A's bit for bit.  features: 'gaussian' (unrelated to the
+    labels: every column ranks before some query's last positive, the count
+    kernels' worst case) or 'clustered' (_clustered_feats)."""
+    from pps_amd import reid_dataset_evaluator as gev
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(0)
+    qid, qcam, gid, gcam = _market_labels(Q, G)
+    if features == 'clustered':
+        cent = torch.randn(int(max(qid.max(), gid.max())) + 1, D, generator=gen, device='cuda')
+        q, gal = _clustered_feats(cent, qid, gen), _clustered_feats(cent, gid, gen)
+        del cent
+    else:
+        q, gal = _feats(Q, D, gen), _feats(G, D, gen)
+    index = ops.GalleryIndex(gal, math='h2')
+    mi = ops.MatchIndex(qid, qcam, gid, gcam)
+    out = ops.dist_buffer(Q, G, 'cuda')
+
+    best_a = None
+    for t in range(ops.h2_num_tiles()):
+        ops.compute_dist(q, index, out=out, math='h2', tile=t)
+        ms, _ = _time(lambda: ops.compute_dist(q, index, out=out, math='h2', tile=t))
+        if best_a is None or ms < best_a[1]:
+            best_a = (t, ms)
+    tile_a = best_a[0]
+
+    # the kernels alone, on the lists and sorted positives both paths share
+    q_split = ops.split_h2_tiled(q)
+    pd, pi, pc, junk = ops.collect_matches_h2(q_split, index, mi)
+    sp = ops.rank_prepare(pd[None], pi[None], pc[None])
+    best_b, sweep = None, {}
+    for t in range(1, ops.search_num_tiles()):
+        for s in [0, 1, 2, 4, 8, 16]:
+            ops.rank_count_h2(q_split, index, 0, sp, junk, segments=s, tile=t)
+            ms, _ = _time(lambda: ops.rank_count_h2(q_split, index, 0, sp, junk, segments=s,
+                                                    tile=t))
+            sweep['tile%d_segments%d' % (t, s)] = round(ms, 3)
+            if best_b is None or ms < best_b[2]:
+                best_b = (t, s, ms)
+    tile_b, seg_b = best_b[0], best_b[1]
+
+    def path_a():
+        ops.compute_dist(q, index, out=out, math='h2', tile=tile_a)
+        return gev.rank_eval(out, qid, gid, qcam, gcam, index=mi)
+
+    def path_b():
+        return ops.rank_eval_fused(q, index, qid, qcam, gid, gcam, segments=seg_b, tile=tile_b,
+                                   match_index=mi)
+
+    parts = dict(
+        distmat=lambda: ops.compute_dist(q, index, out=out, math='h2', tile=tile_a),
+        collect_matches=lambda: ops.collect_matches(out, mi),
+        rank_count_stream=lambda: ops.rank_count_stream(out, 0, sp, junk),
+        split_queries=lambda: ops.split_h2_tiled(q),
+        collect_matches_h2=lambda: ops.collect_matches_h2(q_split, index, mi),
+        rank_count_h2=lambda: ops.rank_count_h2(q_split, index, 0, sp, junk, segments=seg_b,
+                                                tile=tile_b))
+    for f in (path_a, path_b) + tuple(parts.values()):
+        f()
+    ta, tb = [], []
+    tparts = dict((n, []) for n in parts)
+    for _ in range(max(reps, 5)):
+        ms, ra = _time(path_a)
+        ta.append(ms)
+        ms, rb = _time(path_b)
+        tb.append(ms)
+        for n, f in parts.items():
+            tparts[n].append(_time(f)[0])
+    equal = (torch.equal(ra[0].view(torch.int64), rb[0].view(torch.int64)) and
+             torch.equal(ra[1], rb[1]) and torch.equal(ra[2], rb[2]))
+    if not equal:
+        raise RuntimeError('bench_rank %s: rank_eval_fused differs from rank_eval' % name)
+    valid = ra[1].bool()
+    mAP = float(ra[0][valid].sum() / valid.sum())
+    hits = int(valid.sum())
+    # the share of the Q x G columns at or before their query's last positive
+    binned = float(ops.rank_count_stream(out, 0, sp, junk)[0].sum()) / (float(Q) * G)
+    del out, ra, rb
+    torch.cuda.empty_cache()
+
+    def alloc_a():
+        o = ops.dist_buffer(Q, G, 'cuda')
+        ops.compute_dist(q, index, out=o, math='h2', tile=tile_a)
+        gev.rank_eval(o, qid, gid, qcam, gcam, index=mi)
+    peak_a = _peak(alloc_a)
+    torch.cuda.empty_cache()
+    peak_b = _peak(path_b)
+    a_ms, b_ms = _median(ta), _median(tb)
+    res = dict(shape=name, leg='rank', features=features, Q=Q, G=G, D=D,
+               list_width=int(sp.sorted_d.shape[1]), valid_queries=int(hits), mAP=mAP,
+               binned_fraction=binned,
+               materialised_ms=round(a_ms, 3), fused_ms=round(b_ms, 3),
+               fused_over_materialised=round(b_ms / a_ms, 4),
+               materialised_tile=tile_a, fused_tile=tile_b, fused_segments=seg_b,
+               materialised_peak_bytes=int(peak_a), fused_peak_bytes=int(peak_b),
+               outputs_equal=bool(equal), rank_count_h2_sweep_ms=sweep,
+               materialised_ms_all=[round(x, 3) for x in ta],
+               fused_ms_all=[round(x, 3) for x in tb])
+    for n, t in tparts.items():
+        res[n + '_ms'] = round(_median(t), 3)
+        res[n + '_ms_all'] = [round(x, 3) for x in t]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--shapes', default='market,shard')
     ap.add_argument('--segmented', action='store_true')
     ap.add_argument('--exclude', action='store_true')
+    ap.add_argument('--rank', action='store_true')
     ap.add_argument('--parent-lib', default=None)
     a = ap.parse_args()
     from pps_amd import ops
     for name in [s for s in a.shapes.split(',') if s]:
         Q, G, D, k = SHAPES[name]
-        if a.exclude:
+        if a.rank:
+            for features in ('gaussian', 'clustered'):
+                print(json.dumps(bench_rank(name, Q, G, D, a.reps, ops, features)), flush=True)
+                torch.cuda.empty_cache()
+        elif a.exclude:
             print(json.dumps(bench_exclude(name, Q, G, D, k, a.reps, ops, a.parent_lib,
                                            cmc=name == 'shard')), flush=True)
         else:
