@@ -541,6 +541,33 @@ int pps_rank_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, co
                             int tile, void* workspace, int64_t ws_bytes, int32_t* hist,
                             int32_t* before, void* stream);
 
+/* The fractional and the separate-camera CMC without the [Q, G] matrix:
+ * pps_cmc_counts with the planes in place of dist.  hist [Q][Ptot] receives
+ * exactly the counts pps_cmc_counts adds on the matrix pps_distmat_h2_tiled
+ * would write -- every valid column binned at b = the number of positives
+ * whose (distance, global index) key is below its own, counted when
+ * b < pos_total[q] -- so pps_cmc_finalize gives the same CMC rows, bit for
+ * bit.  Operands and their checks are pps_rank_count_h2_tiled's (planes,
+ * g_offset + G < 2^31, segments, tile, Ptot <= pps_rank_count_h2_max_p() else
+ * PPS_ERR_CAPACITY before anything is launched, workspace sized by
+ * pps_rank_count_h2_workspace_bytes: 0 today, null accepted).  Valid columns:
+ *  - qcam == gcam == NULL: every column, and this gallery's junk lists (from
+ *    pps_collect_matches_h2; all three required, Jmax > 0) are taken back out;
+ *  - both given (separate_camera_set; qcam [Q], gcam [G] = this gallery's
+ *    LOCAL cams): a column counts iff gcam[c] != qcam[q]; the junk lists are
+ *    not read and may be null.
+ * Exactly one of qcam / gcam null is PPS_ERR_INVALID_ARG.  Counts are ADDED
+ * into hist (zeroed, or carrying earlier segments' counts); rows with
+ * pos_total == 0 are skipped; Q == 0 or G == 0 adds nothing. */
+int pps_cmc_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                           const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                           int D, int metric, int64_t g_offset, int Ptot,
+                           const float* sorted_d, const int32_t* sorted_idx,
+                           const int32_t* pos_total, const int32_t* qcam, const int32_t* gcam,
+                           int Jmax, const float* junk_d, const int32_t* junk_idx,
+                           const int32_t* junk_cnt, int segments, int tile,
+                           void* workspace, int64_t ws_bytes, int32_t* hist, void* stream);
+
 /* k-reciprocal re-ranking (reid_dataset_evaluator.py:442-519): out [Q][G] =
  * re_ranking(q_g, q_q, g_g, k1, k2, lambda) with the reference's float32
  * operand order for V, V_qe and the Jaccard sums; ties in the initial rank use

@@ -102,6 +102,9 @@ SIGNATURES = {
     'pps_rank_count_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
                                 c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
                                 c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
+    'pps_cmc_count_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                               c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
+                               c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],

@@ -44,6 +44,11 @@
 //    distances) are taken back out by a small follow-up kernel on the same
 //    stream, as rank_count_stream's chunk 0 does.
 //
+// c) cmc_count_h2 (the fractional and the separate-camera CMC): b)'s kernel
+//    with cmc_count_kernel's key bins in place of the distance bins (its KEY
+//    parameter, described at kBinDist below) -- pps_cmc_counts on the h2
+//    matrix, exactly; pps_cmc_finalize runs unchanged after it.
+//
 // No workgroup waits on another; nothing is launched cooperatively.
 #include <algorithm>
 
@@ -163,14 +168,32 @@ struct RankH2Args {
   const int32_t* sorted_idx;
   const int32_t* pos_total;       // [Q]
   int32_t* hist;                  // [Q][Ptot]
-  int32_t* before;                // [Q]
+  int32_t* before;                // [Q] (distance bins only)
+  const int32_t* qcam;            // [Q], this gallery's local [G]: separate-camera key bins
+  const int32_t* gcam;
 };
+
+// What a valid column adds to hist (the kernel's KEY parameter):
+//  kBinDist    rank_count_stream's bins, lower_bound(sorted_d, d), and `before`;
+//  kBinKey     cmc_count_kernel's: b = #positives whose (distance, global index)
+//              key is below the column's own, counted when b < P; every column
+//              is valid (the junk entries are taken back out afterwards);
+//  kBinKeyCam  the same bins, a column valid iff gcam[c] != qcam[q]
+//              (separate_camera_set; no junk lists).
+// The key bin is the distance bin unless d equals a positive's distance
+// (s_S[lo] == d): then the column goes past the positives of that tie group
+// with a lower global index, found by a binary search on sorted_idx over
+// [lo, P) in global memory (L2) -- the tie group may leave the staged block,
+// and a second 8 KiB of index blocks would not fit beside the 192 x 192 tile.
+// A positive's own column takes that path (b = its own position), so it runs
+// at least P times per row, and otherwise only for copied gallery rows.
+constexpr int kBinDist = 0, kBinKey = 1, kBinKeyCam = 2;
 
 __device__ inline float uniform_f32(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+template <int BM, int BN, int WM, int WN, int NS, int KEY>
 __global__ void __launch_bounds__(64 * WM * WN)
 rank_count_h2_kernel(GemmParams p, RankH2Args a) {
   using T = H2Tile<BM, BN, WM, WN, NS>;
@@ -222,7 +245,7 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
         if (P > 0) {
           s_df[row] = a.sorted_d[gr * Ptot];
           s_dmax[row] = a.sorted_d[gr * Ptot + P - 1];
-          s_idf[row] = a.sorted_idx[gr * Ptot];
+          if (KEY == kBinDist) s_idf[row] = a.sorted_idx[gr * Ptot];
         }
       }
       s_P[row] = P;
@@ -253,12 +276,14 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
         // this lane's columns of the pass: norms and scales once for all rows
         bool ok[CS];
         float gn[CS], rb[CS];
+        int cam[CS];
 #pragma unroll
         for (int j = 0; j < CS; ++j) {
           const int c = j * 64 + lane;
           ok[j] = c < BNH && c0h + c < nrem;
           gn[j] = ok[j] ? p.norm_b[n0 + c0h + c] : 0.f;
           rb[j] = ok[j] ? p.rs_b[n0 + c0h + c] : 0.f;
+          if (KEY == kBinKeyCam) cam[j] = ok[j] ? a.gcam[n0 + c0h + c] : 0;
         }
         float Spre[NB];     // row pre_row's first list block, requested a row ahead
         int pre_row = -1;
@@ -273,6 +298,7 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
           const float qn = p.norm_a[gr];
           const float ra = p.rs_a[gr];
           const float dmax = uniform_f32(s_dmax[row]);
+          const int qc = KEY == kBinKeyCam ? a.qcam[gr] : 0;   // wave-uniform
           float d[CS];
           bool hit[CS];
           int nh = 0;
@@ -282,19 +308,22 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
             // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
             const float dot = ok[j] ? t[row * LD + c] : 0.f;
             d[j] = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
-            hit[j] = ok[j] && d[j] <= dmax;
+            hit[j] = ok[j] && d[j] <= dmax;   // d > dmax: ordered after every positive
+            if (KEY == kBinKeyCam) hit[j] = hit[j] && cam[j] != qc;
             nh += __popcll(__ballot(hit[j]));
           }
           if (nh == 0) continue;   // nothing of this pass ranks up to the last positive
-          const float df = uniform_f32(s_df[row]);
-          const int64_t idf = __builtin_amdgcn_readfirstlane(s_idf[row]);
-          int nbef = 0;
+          if constexpr (KEY == kBinDist) {
+            const float df = uniform_f32(s_df[row]);
+            const int64_t idf = __builtin_amdgcn_readfirstlane(s_idf[row]);
+            int nbef = 0;
 #pragma unroll
-          for (int j = 0; j < CS; ++j) {
-            const int64_t gc = a.g_offset + n0 + c0h + j * 64 + lane;   // global column
-            nbef += __popcll(__ballot(hit[j] && (d[j] < df || (d[j] == df && gc < idf))));
+            for (int j = 0; j < CS; ++j) {
+              const int64_t gc = a.g_offset + n0 + c0h + j * 64 + lane;   // global column
+              nbef += __popcll(__ballot(hit[j] && (d[j] < df || (d[j] == df && gc < idf))));
+            }
+            if (nbef && lane == 0) atomicAdd(a.before + gr, nbef);
           }
-          if (nbef && lane == 0) atomicAdd(a.before + gr, nbef);
           const float* sd = a.sorted_d + gr * Ptot;
           int32_t* hq = a.hist + gr * Ptot;
           // the list's first block: requested while the previous row was binned, or now
@@ -337,7 +366,22 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
               // lower_bound over the whole list falls in [p0, p0 + PB)
               const bool inb = hit[j] && (p0 == 0 || d[j] > prev) && d[j] <= last;
               done += __popcll(__ballot(inb));
-              if (inb) atomicAdd(hq + p0 + lo[j], 1);
+              if constexpr (KEY == kBinDist) {
+                if (inb) atomicAdd(hq + p0 + lo[j], 1);
+              } else if (inb) {
+                int b = p0 + lo[j];   // < P: some positive is >= d
+                if (s_S[lo[j]] == d[j]) {
+                  // the tie group starts at b: go past its members below this column
+                  const int gc = (int)(a.g_offset + n0 + c0h + j * 64 + lane);
+                  const int32_t* si = a.sorted_idx + gr * Ptot;
+                  int hi = P;
+                  while (b < hi) {
+                    const int mid = (b + hi) >> 1;
+                    if (sd[mid] == d[j] && si[mid] < gc) b = mid + 1; else hi = mid;
+                  }
+                }
+                if (b < P) atomicAdd(hq + b, 1);
+              }
             }
             prev = last;
             if (done >= nh || p0 + PB >= P) break;
@@ -385,13 +429,84 @@ rank_h2_junk_kernel(int64_t Q, int Ptot, const float* __restrict__ sorted_d,
   if (lane == 0 && nb) atomicAdd(before + q, -nb);
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+// The same for the key bins (cmc_count_kernel's junk loop): an entry leaves
+// the bin its own column was counted in, b = #positives with key < (d, index).
+__global__ void __launch_bounds__(64 * kJunkWaves)
+cmc_h2_junk_kernel(int64_t Q, int Ptot, const float* __restrict__ sorted_d,
+                   const int32_t* __restrict__ sorted_idx,
+                   const int32_t* __restrict__ pos_total, int Jmax,
+                   const float* __restrict__ junk_d, const int32_t* __restrict__ junk_idx,
+                   const int32_t* __restrict__ junk_cnt, int32_t* __restrict__ hist) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * kJunkWaves + (threadIdx.x >> 6);
+  if (q >= Q) return;
+  const int P = min(pos_total[q], Ptot);
+  if (P <= 0) return;
+  const float* sd = sorted_d + q * Ptot;
+  const int32_t* si = sorted_idx + q * Ptot;
+  const float dmax = sd[P - 1];
+  const int nj = min(junk_cnt[q], Jmax);
+  for (int j = lane; j < nj; j += 64) {
+    const float d = junk_d[q * Jmax + j];
+    if (d > dmax) continue;
+    const int gi = junk_idx[q * Jmax + j];
+    int lo = 0, hi = P;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sd[mid] < d || (sd[mid] == d && si[mid] < gi)) lo = mid + 1; else hi = mid;
+    }
+    if (lo < P) atomicAdd(hist + q * Ptot + lo, -1);
+  }
+}
+
+template <int BM, int BN, int WM, int WN, int NS, int KEY>
 static int launch_rank_count(const GemmParams& p, const RankH2Args& a, hipStream_t st) {
   const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
-  hipLaunchKernelGGL((rank_count_h2_kernel<BM, BN, WM, WN, NS>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((rank_count_h2_kernel<BM, BN, WM, WN, NS, KEY>), dim3((unsigned)grid),
                      dim3(64 * WM * WN), 0, st, p, a);
   PPS_CHECK_LAUNCH("rank_count_h2_kernel");
   return PPS_OK;
+}
+
+// the two tile shapes of one binning mode
+template <int KEY>
+static int launch_rank_count_tile(int tile, const GemmParams& p, const RankH2Args& a,
+                                  hipStream_t st) {
+  return tile == 2 ? launch_rank_count<192, 192, 2, 4, 3, KEY>(p, a, st)
+                   : launch_rank_count<256, 256, 2, 4, 2, KEY>(p, a, st);
+}
+
+// The plan and the operands the two count entries share (their guards passed).
+static void rank_count_plan(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                            int D, int metric, int64_t g_offset, int Ptot,
+                            const float* sorted_d, const int32_t* sorted_idx,
+                            const int32_t* pos_total, int segments, int tile, int32_t* hist,
+                            GemmParams& p, RankH2Args& a) {
+  int BM, BN;
+  search_tile_shape(tile, BM, BN);
+  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
+  const int64_t panels = cdiv(Q, BM), tiles_n = cdiv(G, BN);
+  const int64_t S0 = fused_segments(Q, G, segments, BM, BN);
+  a.tiles_n = (int)tiles_n;
+  a.tps = (int)cdiv(tiles_n, S0);
+  a.S = (int)cdiv(tiles_n, a.tps);   // no empty segment
+  a.items = panels * a.S;
+  a.g_offset = g_offset;
+  a.Ptot = Ptot;
+  a.sorted_d = sorted_d; a.sorted_idx = sorted_idx; a.pos_total = pos_total;
+  a.hist = hist;
+
+  p.splitk = 1;
+  p.tiled = 3;
+  p.a3 = q2t; p.a_plane = Qp * D; p.a_bytes = (uint32_t)(2 * Qp * D * 2);
+  p.M = (int)Q;
+  p.b3 = g2t; p.b_plane = Gp * D; p.b_bytes = (uint32_t)(2 * Gp * D * 2);
+  p.Ncol = (int)G;
+  p.Kloop = D;
+  p.norm_a = qsq; p.norm_b = gsq;
+  p.rs_a = qrs; p.rs_b = grs;
+  p.metric = metric;
 }
 
 // the checks the planes arguments share with pps_search_h2_tiled (same texts)
@@ -483,40 +598,64 @@ int pps_rank_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, co
   PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
 
-  int BM, BN;
-  search_tile_shape(tile, BM, BN);
-  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
-  const int64_t panels = cdiv(Q, BM), tiles_n = cdiv(G, BN);
-  const int64_t S0 = fused_segments(Q, G, segments, BM, BN);
-  RankH2Args a{};
-  a.tiles_n = (int)tiles_n;
-  a.tps = (int)cdiv(tiles_n, S0);
-  a.S = (int)cdiv(tiles_n, a.tps);   // no empty segment
-  a.items = panels * a.S;
-  a.g_offset = g_offset;
-  a.Ptot = Ptot;
-  a.sorted_d = sorted_d; a.sorted_idx = sorted_idx; a.pos_total = pos_total;
-  a.hist = hist; a.before = before;
-
   GemmParams p{};
-  p.splitk = 1;
-  p.tiled = 3;
-  p.a3 = q2t; p.a_plane = Qp * D; p.a_bytes = (uint32_t)(2 * Qp * D * 2);
-  p.M = (int)Q;
-  p.b3 = g2t; p.b_plane = Gp * D; p.b_bytes = (uint32_t)(2 * Gp * D * 2);
-  p.Ncol = (int)G;
-  p.Kloop = D;
-  p.norm_a = qsq; p.norm_b = gsq;
-  p.rs_a = qrs; p.rs_b = grs;
-  p.metric = metric;
-
-  const int rc = tile == 2 ? launch_rank_count<192, 192, 2, 4, 3>(p, a, st)
-                           : launch_rank_count<256, 256, 2, 4, 2>(p, a, st);
+  RankH2Args a{};
+  rank_count_plan(q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, g_offset, Ptot, sorted_d,
+                  sorted_idx, pos_total, segments, tile, hist, p, a);
+  a.before = before;
+  const int rc = launch_rank_count_tile<kBinDist>(tile, p, a, st);
   if (rc != PPS_OK) return rc;
   const unsigned grid = (unsigned)((Q + kJunkWaves - 1) / kJunkWaves);
   hipLaunchKernelGGL(rank_h2_junk_kernel, dim3(grid), dim3(64 * kJunkWaves), 0, st, Q, Ptot,
                      sorted_d, sorted_idx, pos_total, Jmax, junk_d, junk_idx, junk_cnt, hist,
                      before);
   PPS_CHECK_LAUNCH("rank_h2_junk_kernel");
+  return PPS_OK;
+}
+
+int pps_cmc_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                           const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                           int D, int metric, int64_t g_offset, int Ptot,
+                           const float* sorted_d, const int32_t* sorted_idx,
+                           const int32_t* pos_total, const int32_t* qcam, const int32_t* gcam,
+                           int Jmax, const float* junk_d, const int32_t* junk_idx,
+                           const int32_t* junk_cnt, int segments, int tile,
+                           void* workspace, int64_t ws_bytes, int32_t* hist, void* stream) {
+  PPS_ENFORCE(sorted_d && sorted_idx && pos_total && hist, "null pointer");
+  PPS_ENFORCE((qcam == nullptr) == (gcam == nullptr),
+              "qcam and gcam are given together (separate_camera_set) or not at all");
+  PPS_ENFORCE(gcam || (junk_d && junk_idx && junk_cnt && Jmax > 0),
+              "without separate_camera_set the junk lists are required");
+  PPS_ENFORCE_H2_PLANES(Q, G, D, metric);
+  PPS_ENFORCE(Ptot > 0, "bad shape");
+  PPS_ENFORCE(g_offset >= 0 && g_offset + G < (1ll << 31), "gallery indices must fit int32");
+  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
+  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
+              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
+  if (Ptot > kRankH2MaxP) {
+    set_error("pps_cmc_count_h2_tiled: Ptot = " + std::to_string(Ptot) +
+              " merged positives per query, the fused count takes at most " +
+              std::to_string(kRankH2MaxP) + " (pps_rank_count_h2_max_p)");
+    return PPS_ERR_CAPACITY;
+  }
+  (void)workspace;   // pps_rank_count_h2_workspace_bytes is 0: nothing to check
+  (void)ws_bytes;
+  if (Q == 0 || G == 0) return PPS_OK;
+  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
+  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+
+  GemmParams p{};
+  RankH2Args a{};
+  rank_count_plan(q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, g_offset, Ptot, sorted_d,
+                  sorted_idx, pos_total, segments, tile, hist, p, a);
+  a.qcam = qcam; a.gcam = gcam;
+  if (gcam) return launch_rank_count_tile<kBinKeyCam>(tile, p, a, st);
+  const int rc = launch_rank_count_tile<kBinKey>(tile, p, a, st);
+  if (rc != PPS_OK) return rc;
+  const unsigned grid = (unsigned)((Q + kJunkWaves - 1) / kJunkWaves);
+  hipLaunchKernelGGL(cmc_h2_junk_kernel, dim3(grid), dim3(64 * kJunkWaves), 0, st, Q, Ptot,
+                     sorted_d, sorted_idx, pos_total, Jmax, junk_d, junk_idx, junk_cnt, hist);
+  PPS_CHECK_LAUNCH("cmc_h2_junk_kernel");
   return PPS_OK;
 }

@@ -30,7 +30,7 @@ static_assert(16 * kRankMergeCap <= kLdsBytesGfx950, "rank_prepare LDS exceeds t
 // 1 = 256 x 256 two-stage, 2 = 192 x 192 three-stage
 constexpr int kSearchNumTiles = 3;
 constexpr int kSearchSlots = 256;    // workgroups launched at most: one per CU (LDS-bound residency)
-// rank_count_h2: longest merged positive list (Ptot).  The kernel bins a pass
+// rank_count_h2 / cmc_count_h2: longest merged positive list (Ptot).  The kernel bins a pass
 // of columns against the list with one ballot per positive; beyond the cap
 // rank_count_stream's binary search on the matrix is the right algorithm
 constexpr int kRankH2MaxP = 1024;

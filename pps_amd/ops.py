@@ -887,6 +887,16 @@ def _h2_operands(fn, q_split, index):
             _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G, D)
 
 
+def _workspace_arg(fn, workspace):
+    """(pointer, bytes) of the optional workspace of the fused count entries."""
+    if workspace is None:
+        return 0, 0
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
+            not workspace.is_contiguous()):
+        raise RuntimeError('%s: workspace must be a contiguous device tensor' % fn)
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size()
+
+
 def collect_matches_h2(q_split, index, match_index, metric='euclidean', g_offset=0, pmax=None):
     """collect_matches without the matrix (pps_collect_matches_h2): q_split =
     split_h2_tiled(queries), index an h2 GalleryIndex, match_index the
@@ -936,12 +946,7 @@ def rank_count_h2(q_split, index, g_offset, sp, junk, metric='euclidean', hist=N
         before = torch.zeros((Q,), dtype=torch.int32, device=dev)
     if tuple(hist.shape) != (Q, Ptot) or tuple(before.shape) != (Q,):
         raise RuntimeError('rank_count_h2: hist must be [%d, %d] and before [%d]' % (Q, Ptot, Q))
-    ws_ptr = ws_bytes = 0
-    if workspace is not None:
-        if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
-                not workspace.is_contiguous()):
-            raise RuntimeError('rank_count_h2: workspace must be a contiguous device tensor')
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    ws_ptr, ws_bytes = _workspace_arg('rank_count_h2', workspace)
     call('pps_rank_count_h2_tiled', *(args + (
         METRICS[metric], int(g_offset), Ptot, _dev(sp.sorted_d, 'sorted_d'),
         _dev(sp.sorted_idx, 'sorted_idx', torch.int32),
@@ -950,6 +955,47 @@ def rank_count_h2(q_split, index, g_offset, sp, junk, metric='euclidean', hist=N
         int(segments), int(tile), ws_ptr, ws_bytes, _dev(hist, 'hist', torch.int32),
         _dev(before, 'before', torch.int32), _stream())))
     return hist, before
+
+
+def cmc_counts_h2(q_split, index, g_offset, sp, junk, match_index=None,
+                  separate_camera_set=False, metric='euclidean', hist=None, segments=0, tile=0,
+                  workspace=None):
+    """cmc_counts without the matrix (pps_cmc_count_h2_tiled): the additive
+    per-positive key bins of this gallery (shard, segment) against the
+    SortedPositives sp, distances computed on the fly from q_split and the h2
+    GalleryIndex -- the counts cmc_counts gives on compute_dist(q, index,
+    math='h2'), exactly.  junk = this gallery's junk lists from
+    collect_matches_h2; with separate_camera_set the MatchIndex's qcam / gcam
+    drop every same-camera column instead and junk is not read (None is
+    accepted).  hist accumulates when given.  sp's width must not exceed
+    rank_count_h2_max_p().  segments / tile: as in search (same counts)."""
+    args = _h2_operands('cmc_counts_h2', q_split, index)
+    Q, G = args[1], args[7]
+    Ptot = sp.sorted_d.shape[1]
+    if hist is None:
+        hist = torch.zeros((Q, Ptot), dtype=torch.int32, device=q_split[0].device)
+    if tuple(hist.shape) != (Q, Ptot):
+        raise RuntimeError('cmc_counts_h2: hist must be [%d, %d]' % (Q, Ptot))
+    qc = gc = jmax = jd = ji = jc = 0
+    if separate_camera_set:
+        if match_index is None or (Q, G) != (match_index.Q, match_index.G):
+            raise RuntimeError('cmc_counts_h2: separate_camera_set needs the MatchIndex of '
+                               'the %d queries and %d gallery rows' % (Q, G))
+        qc = _dev(match_index.qcam, 'qcam', torch.int32)
+        gc = _dev(match_index.gcam, 'gcam', torch.int32)
+    else:
+        junk_d, junk_idx, junk_cnt = junk
+        jmax = junk_d.shape[1]
+        jd, ji = _dev(junk_d, 'junk_d'), _dev(junk_idx, 'junk_idx', torch.int32)
+        jc = _dev(junk_cnt, 'junk_cnt', torch.int32)
+    ws_ptr, ws_bytes = _workspace_arg('cmc_counts_h2', workspace)
+    call('pps_cmc_count_h2_tiled', *(args + (
+        METRICS[metric], int(g_offset), Ptot, _dev(sp.sorted_d, 'sorted_d'),
+        _dev(sp.sorted_idx, 'sorted_idx', torch.int32),
+        _dev(sp.pos_total, 'pos_total', torch.int32), qc, gc, jmax, jd, ji, jc,
+        int(segments), int(tile), ws_ptr, ws_bytes, _dev(hist, 'hist', torch.int32),
+        _stream())))
+    return hist
 
 
 def _gallery_parts(fn, q, gallery):
@@ -1012,24 +1058,69 @@ def rank_eval_fused(q, gallery, qid, qcam, gid, gcam, metric='euclidean', segmen
     0.19 GB peak where that path holds the 5.1 GB block -- and a path for a
     gallery split over several indexes, which one compute_dist call cannot
     take."""
-    parts = _gallery_parts('rank_eval_fused', q, gallery)
+    st = _fused_lists('rank_eval_fused', q, gallery, qid, qcam, gid, gcam, metric, match_index)
+    dev = q.device
+    if st is None:
+        return (torch.empty((0,), dtype=torch.float64, device=dev),
+                torch.empty((0,), dtype=torch.int32, device=dev),
+                torch.empty((0,), dtype=torch.int32, device=dev))
+    sp = st.sp
+    hist = torch.zeros(tuple(sp.sorted_d.shape), dtype=torch.int32, device=dev)
+    before = torch.zeros((q.shape[0],), dtype=torch.int32, device=dev)
+    for p, a, mi, junk, fused in st.segments():
+        if fused:
+            rank_count_h2(st.q_split, p, a, sp, junk, metric, hist, before, segments, tile)
+        else:
+            dist = st.block(p)
+            rank_count_stream(dist, a, sp, junk, hist, before)
+            del dist
+    return ap_finalize(sp.sorted_d, sp.pos_total, hist, before)
+
+
+class _FusedLists(object):
+    """What _fused_lists leaves for the counts: the gallery segments with their
+    start rows, MatchIndex objects and junk lists, the queries' split, the
+    merged SortedPositives."""
+
+    def __init__(self, parts, starts, mis, junks, fusable, q_split, sp, block, kept):
+        self.parts, self.starts, self.mis, self.junks = parts, starts, mis, junks
+        self.fusable, self.q_split, self.sp = fusable, q_split, sp
+        self._block, self._kept = block, kept
+        self.fits = sp.sorted_d.shape[1] <= rank_count_h2_max_p()
+
+    def segments(self):
+        """(segment, its start row, its MatchIndex, its junk lists, whether the
+        fused count applies) per gallery segment."""
+        for p, a, mi, junk, f in zip(self.parts, self.starts[:-1], self.mis, self.junks,
+                                     self.fusable):
+            yield p, int(a), mi, junk, f and self.fits
+
+    def block(self, p):
+        """The segment's [Q, rows] block (a lone segment's, built for the
+        collect, is reused)."""
+        return self._kept if self._kept is not None else self._block(p)
+
+
+def _fused_lists(fn, q, gallery, qid, qcam, gid, gcam, metric, match_index):
+    """The front half rank_eval_fused and cmc_eval_fused share: the gallery as
+    segments, one MatchIndex and one collect per segment, one rank_prepare over
+    the stacked lists, the trim to max_positives.  None when Q == 0."""
+    parts = _gallery_parts(fn, q, gallery)
     if len(parts) > RANK_FUSED_MAX_SEGMENTS:
-        raise RuntimeError('rank_eval_fused: %d gallery segments, pps_rank_prepare merges at '
-                           'most %d lists per query' % (len(parts), RANK_FUSED_MAX_SEGMENTS))
+        raise RuntimeError('%s: %d gallery segments, pps_rank_prepare merges at '
+                           'most %d lists per query' % (fn, len(parts), RANK_FUSED_MAX_SEGMENTS))
     qid, qcam, gid, gcam = (np.asarray(a).reshape(-1) for a in (qid, qcam, gid, gcam))
     Q, D = q.shape
     starts = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
     if len(qid) != Q or len(qcam) != Q or len(gid) != starts[-1] or len(gcam) != starts[-1]:
-        raise RuntimeError('rank_eval_fused: %d queries / %d gallery rows, ids and cams of '
-                           '%d / %d / %d / %d' % (Q, starts[-1], len(qid), len(qcam), len(gid),
-                                                  len(gcam)))
+        raise RuntimeError('%s: %d queries / %d gallery rows, ids and cams of '
+                           '%d / %d / %d / %d' % (fn, Q, starts[-1], len(qid), len(qcam),
+                                                  len(gid), len(gcam)))
     if starts[-1] >= 2 ** 31:
-        raise RuntimeError('rank_eval_fused: gallery indices must fit int32')
+        raise RuntimeError('%s: gallery indices must fit int32' % fn)
     dev = q.device
     if Q == 0:
-        return (torch.empty((0,), dtype=torch.float64, device=dev),
-                torch.empty((0,), dtype=torch.int32, device=dev),
-                torch.empty((0,), dtype=torch.int32, device=dev))
+        return None
     q_split = None
     if D % 32 == 0 and q.is_contiguous() and any(p.h2 is not None for p in parts):
         q_split = split_h2_tiled(q)   # once, as compute_dist splits them
@@ -1043,8 +1134,8 @@ def rank_eval_fused(q, gallery, qid, qcam, gid, gcam, metric='euclidean', segmen
     else:
         mis = [match_index] if isinstance(match_index, MatchIndex) else list(match_index)
         if [(m.Q, m.G) for m in mis] != [(Q, p.shape[0]) for p in parts]:
-            raise RuntimeError('rank_eval_fused: match_index does not fit the queries and '
-                               'the gallery segments')
+            raise RuntimeError('%s: match_index does not fit the queries and '
+                               'the gallery segments' % fn)
     pmax = max(mi.capacity for mi in mis)
     lists, junks, kept = [], [], None
     for p, mi, a, f in zip(parts, mis, starts[:-1], fusable):
@@ -1064,18 +1155,40 @@ def rank_eval_fused(q, gallery, qid, qcam, gid, gcam, metric='euclidean', segmen
     if ptrue < sp.sorted_d.shape[1]:   # the tail is padding for every query
         sp = SortedPositives(sp.sorted_d[:, :ptrue].contiguous(),
                              sp.sorted_idx[:, :ptrue].contiguous(), sp.pos_total, sp.cells)
-    Ptot = sp.sorted_d.shape[1]
-    hist = torch.zeros((Q, Ptot), dtype=torch.int32, device=dev)
-    before = torch.zeros((Q,), dtype=torch.int32, device=dev)
-    fits = Ptot <= rank_count_h2_max_p()
-    for p, a, f, junk in zip(parts, starts[:-1], fusable, junks):
-        if f and fits:
-            rank_count_h2(q_split, p, int(a), sp, junk, metric, hist, before, segments, tile)
+    return _FusedLists(parts, starts, mis, junks, fusable, q_split, sp, block, kept)
+
+
+def cmc_eval_fused(q, gallery, qid, qcam, gid, gcam, topk=100, separate_camera_set=False,
+                   first_match_break=False, metric='euclidean', segments=0, tile=0,
+                   match_index=None):
+    """(ret [Q, topk] float64, valid [Q] int32): the per-query CMC rows of the
+    reference's cmc (fractional or first-match, with or without
+    separate_camera_set; not single_gallery_shot) -- what cmc_finalize returns
+    for cmc_counts on compute_dist(q, gallery, math='h2'), bit for bit --
+    without the [Q, G] matrix.  rank_eval_fused's front half (the gallery as
+    tensor / GalleryIndex / sequence of segments, one MatchIndex and one
+    collect per segment, one rank_prepare, the trim to max_positives), then one
+    keyed count per segment (pps_cmc_count_h2_tiled) into one hist and
+    pps_cmc_finalize.  Arguments and fallbacks are rank_eval_fused's: a segment
+    holding an x3 split, D % 32 != 0, non-contiguous queries or merged lists
+    wider than rank_count_h2_max_p() take compute_dist + collect_matches /
+    cmc_counts on that segment's block and give the materialised answer."""
+    st = _fused_lists('cmc_eval_fused', q, gallery, qid, qcam, gid, gcam, metric, match_index)
+    dev = q.device
+    if st is None:
+        return (torch.empty((0, int(topk)), dtype=torch.float64, device=dev),
+                torch.empty((0,), dtype=torch.int32, device=dev))
+    sp = st.sp
+    hist = torch.zeros(tuple(sp.sorted_d.shape), dtype=torch.int32, device=dev)
+    for p, a, mi, junk, fused in st.segments():
+        if fused:
+            cmc_counts_h2(st.q_split, p, a, sp, junk, mi, separate_camera_set, metric, hist,
+                          segments, tile)
         else:
-            dist = kept if kept is not None else block(p)
-            rank_count_stream(dist, int(a), sp, junk, hist, before)
+            dist = st.block(p)
+            cmc_counts(dist, a, sp, junk, mi, separate_camera_set, hist)
             del dist
-    return ap_finalize(sp.sorted_d, sp.pos_total, hist, before)
+    return cmc_finalize(sp.pos_total, hist, topk, first_match_break)
 
 
 def re_ranking(q_g, q_q, g_g, k1=20, k2=6, lambda_value=0.3, symmetric=None, whole=False):

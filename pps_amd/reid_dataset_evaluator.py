@@ -245,18 +245,66 @@ def mean_ap_from_features(query_feats, gallery, query_ids=None, gallery_ids=None
     return ap, valid
 
 
+def cmc_from_features(query_feats, gallery, query_ids=None, gallery_ids=None, query_cams=None,
+                      gallery_cams=None, topk=100, separate_camera_set=False,
+                      single_gallery_shot=False, first_match_break=False, average=True,
+                      metric='euclidean'):
+    """cmc (:283-363) without a distance matrix, with cmc's defaults, outputs
+    and 'No valid query' error: the fractional CMC (first_match_break=False),
+    the first-match CMC, and separate_camera_set with either, from
+    ops.cmc_eval_fused (per-positive key bins counted by a kernel that computes
+    the f16x2 distances on the fly).  Equal, bit for bit, to cmc on
+    ops.compute_dist(query_feats, gallery, math='h2').  first_match_break
+    without separate_camera_set takes rank_eval_from_features' first ranks, as
+    cmc takes rank_eval's.  gallery: what rank_eval_from_features takes; the
+    cases that DO materialise a block are ops.rank_eval_fused's.
+    single_gallery_shot needs every query's whole rank list and is rejected:
+    use cmc on a matrix."""
+    if single_gallery_shot:
+        raise RuntimeError('cmc_from_features has no single_gallery_shot mode (it needs the '
+                           'whole rank list of every query); use cmc on a distance matrix')
+    if not isinstance(gallery, (ops.GalleryIndex, list, tuple)):
+        gallery = _to_dev(gallery)
+    q = _to_dev(query_feats)
+    labels = (_host_ids(query_ids), _host_ids(query_cams), _host_ids(gallery_ids),
+              _host_ids(gallery_cams))
+    if first_match_break and not separate_camera_set:
+        _, valid, first = ops.rank_eval_fused(q, gallery, *labels, metric=metric)
+        valid, first = _np(valid).astype(bool), _np(first)
+        ret = np.zeros((len(valid), topk))
+        rows = np.nonzero(valid & (first < topk))[0]
+        ret[rows, first[rows]] = 1
+        ret = ret.cumsum(axis=1)
+    else:
+        ret, valid = ops.cmc_eval_fused(q, gallery, *labels, topk=topk,
+                                        separate_camera_set=separate_camera_set,
+                                        first_match_break=first_match_break, metric=metric)
+        ret, valid = _np(ret), _np(valid).astype(bool)
+    if not valid.any():
+        raise RuntimeError('No valid query')
+    if average:
+        return np.sum(ret, axis=0) / valid.sum()
+    return ret, valid.astype(np.float64)
+
+
 def evaluate_from_features(query_feats, gallery, query_ids, gallery_ids, query_cams,
-                           gallery_cams, metric='euclidean', topk=10):
-    """(mAP, cmc[topk]) of the Market protocol -- mean_ap and
-    cmc(first_match_break=True) -- without a distance matrix: one
+                           gallery_cams, metric='euclidean', topk=10,
+                           separate_camera_set=False, first_match_break=True):
+    """(mAP, cmc[topk]) without a distance matrix.  The defaults are the Market
+    protocol -- mean_ap and cmc(first_match_break=True) -- from one
     rank_eval_from_features pass, scored by scores_from_ranks like evaluate().
-    The fractional CMC (first_match_break=False) and separate_camera_set need
-    pps_cmc_counts' key-based bins, which have no matrix-free kernel: they are
-    out of scope here, use cmc on a matrix (or cmc_from_search for the
-    separate-camera first-match CMC)."""
+    Any other (separate_camera_set, first_match_break) returns the mAP of
+    rank_eval_from_features and the CMC of cmc_from_features with those
+    arguments: two passes over the features."""
     ap, valid, first = rank_eval_from_features(query_feats, gallery, query_ids, gallery_ids,
                                                query_cams, gallery_cams, metric)
-    return scores_from_ranks(ap, valid, first, topk=topk)
+    if first_match_break and not separate_camera_set:
+        return scores_from_ranks(ap, valid, first, topk=topk)
+    mAP, _ = scores_from_ranks(ap, valid, first, topk=topk)
+    return mAP, cmc_from_features(query_feats, gallery, query_ids, gallery_ids, query_cams,
+                                  gallery_cams, topk=topk,
+                                  separate_camera_set=separate_camera_set,
+                                  first_match_break=first_match_break, metric=metric)
 
 
 SGS_MAX_IDS = 16384   # pps_sgs_keys / pps_sgs_groups (include/pps_abi.h)

@@ -52,8 +52,21 @@ collect_matches, rank_count_stream; the query split, collect_matches_h2 = the
 pair-distance kernel, rank_count_h2 = the fused count kernel); and an error
 unless B's per-query ap (float64 bits), valid and first_rank equal A's.
 
+--cmc replaces them by the matrix-free fractional CMC legs, same shapes, labels
+and both kinds of features, once in junk mode and once with
+separate_camera_set:
+
+  A  ops.compute_dist into a preallocated buffer, then cmc on it
+  B  cmc_from_features (no [Q, G] matrix)
+
+alternating under the same repetition scheme (wall clock around a device
+synchronize: both build their MatchIndex on the host); the count kernels alone
+on the same operands -- cmc_counts_h2 in both modes against rank_count_h2, on
+the tile and segment count one timed sweep picks, and cmc_counts on the matrix
+-- peaks, and an error unless B's per-query rows equal A's as float64 bits.
+
   python scripts/bench_search.py [--reps 5] [--shapes market,shard] [--segmented]
-                                 [--exclude [--parent-lib PATH]] [--rank]
+                                 [--exclude [--parent-lib PATH]] [--rank] [--cmc]
 """
 import argparse
 import ctypes
@@ -486,6 +499,118 @@ def bench_rank(name, Q, G, D, reps, ops, features='gaussian'):
     return res
 
 
+def bench_cmc(name, Q, G, D, reps, ops, features='gaussian'):
+    """A = compute_dist into a preallocated buffer + cmc on it, B =
+    cmc_from_features (no [Q, G] matrix), the fractional CMC once in junk mode
+    and once with separate_camera_set; wall clock around a device synchronize
+    (both build their MatchIndex on the host).  Also the count kernels alone
+    on the same operands (device events): cmc_counts_h2 in both modes against
+    rank_count_h2, all three on the tile and segment count one timed sweep of
+    cmc_counts_h2 picks, and cmc_counts on the matrix.  Raises unless B's
+    per-query rows equal A's as float64 bits."""
+    from pps_amd import reid_dataset_evaluator as gev
+    gen = torch.Generator(device='cuda')
+    gen.manual_seed(0)
+    qid, qcam, gid, gcam = _market_labels(Q, G)
+    if features == 'clustered':
+        cent = torch.randn(int(max(qid.max(), gid.max())) + 1, D, generator=gen, device='cuda')
+        q, gal = _clustered_feats(cent, qid, gen), _clustered_feats(cent, gid, gen)
+        del cent
+    else:
+        q, gal = _feats(Q, D, gen), _feats(G, D, gen)
+    index = ops.GalleryIndex(gal, math='h2')
+    mi = ops.MatchIndex(qid, qcam, gid, gcam)
+    out = ops.dist_buffer(Q, G, 'cuda')
+
+    best_a = None
+    for t in range(ops.h2_num_tiles()):
+        ops.compute_dist(q, index, out=out, math='h2', tile=t)
+        ms, _ = _time(lambda: ops.compute_dist(q, index, out=out, math='h2', tile=t))
+        if best_a is None or ms < best_a[1]:
+            best_a = (t, ms)
+    tile_a = best_a[0]
+
+    q_split = ops.split_h2_tiled(q)
+    pd, pi, pc, junk = ops.collect_matches_h2(q_split, index, mi)
+    sp = ops.rank_prepare(pd[None], pi[None], pc[None])
+    best_b, sweep = None, {}
+    for t in range(1, ops.search_num_tiles()):
+        for s in [0, 1, 2, 4, 8, 16]:
+            ops.cmc_counts_h2(q_split, index, 0, sp, junk, segments=s, tile=t)
+            ms, _ = _time(lambda: ops.cmc_counts_h2(q_split, index, 0, sp, junk, segments=s,
+                                                    tile=t))
+            sweep['tile%d_segments%d' % (t, s)] = round(ms, 3)
+            if best_b is None or ms < best_b[2]:
+                best_b = (t, s, ms)
+    tile_b, seg_b = best_b[0], best_b[1]
+
+    def path_a(sep):
+        ops.compute_dist(q, index, out=out, math='h2', tile=tile_a)
+        return gev.cmc(out, qid, gid, qcam, gcam, separate_camera_set=sep, average=False)
+
+    def path_b(sep):
+        return gev.cmc_from_features(q, index, qid, gid, qcam, gcam, separate_camera_set=sep,
+                                     average=False)
+
+    kw = dict(segments=seg_b, tile=tile_b)
+    ops.compute_dist(q, index, out=out, math='h2', tile=tile_a)
+    parts = dict(
+        cmc_counts=lambda: ops.cmc_counts(out, 0, sp, junk),
+        cmc_counts_sepcam=lambda: ops.cmc_counts(out, 0, sp, junk, mi, True),
+        rank_count_h2=lambda: ops.rank_count_h2(q_split, index, 0, sp, junk, **kw),
+        cmc_counts_h2=lambda: ops.cmc_counts_h2(q_split, index, 0, sp, junk, **kw),
+        cmc_counts_h2_sepcam=lambda: ops.cmc_counts_h2(q_split, index, 0, sp, None, mi, True,
+                                                       **kw))
+    res = dict(shape=name, leg='cmc', features=features, Q=Q, G=G, D=D,
+               list_width=int(sp.sorted_d.shape[1]), materialised_tile=tile_a,
+               count_tile=tile_b, count_segments=seg_b, cmc_counts_h2_sweep_ms=sweep)
+    for f in parts.values():
+        f()
+    tparts = dict((n, []) for n in parts)
+    for _ in range(max(reps, 5)):
+        for n, f in parts.items():
+            tparts[n].append(_time(f)[0])
+    for n, t in tparts.items():
+        res[n + '_ms'] = round(_median(t), 3)
+        res[n + '_ms_all'] = [round(x, 3) for x in t]
+    res['cmc_counts_h2_over_rank_count_h2'] = round(
+        res['cmc_counts_h2_ms'] / res['rank_count_h2_ms'], 4)
+    res['cmc_counts_h2_sepcam_over_rank_count_h2'] = round(
+        res['cmc_counts_h2_sepcam_ms'] / res['rank_count_h2_ms'], 4)
+    for sep, mode in ((False, 'junk'), (True, 'sepcam')):
+        path_a(sep)
+        path_b(sep)
+        ta, tb = [], []
+        for _ in range(max(reps, 5)):
+            ms, ra = _wall(lambda: path_a(sep))
+            ta.append(ms)
+            ms, rb = _wall(lambda: path_b(sep))
+            tb.append(ms)
+        equal = (np.array_equal(ra[0].view(np.int64), rb[0].view(np.int64)) and
+                 np.array_equal(ra[1], rb[1]))
+        if not equal:
+            raise RuntimeError('bench_cmc %s (%s): cmc_from_features differs from cmc'
+                               % (name, mode))
+        a_ms, b_ms = _median(ta), _median(tb)
+        res.update({mode + '_materialised_ms': round(a_ms, 3), mode + '_fused_ms': round(b_ms, 3),
+                    mode + '_fused_over_materialised': round(b_ms / a_ms, 4),
+                    mode + '_rows_equal': bool(equal),
+                    mode + '_rank1': float(ra[0][:, 0].sum() / ra[1].sum()),
+                    mode + '_materialised_ms_all': [round(x, 3) for x in ta],
+                    mode + '_fused_ms_all': [round(x, 3) for x in tb]})
+    del out
+    torch.cuda.empty_cache()
+
+    def alloc_a():
+        o = ops.dist_buffer(Q, G, 'cuda')
+        ops.compute_dist(q, index, out=o, math='h2', tile=tile_a)
+        gev.cmc(o, qid, gid, qcam, gcam, average=False)
+    res['materialised_peak_bytes'] = int(_peak(alloc_a))
+    torch.cuda.empty_cache()
+    res['fused_peak_bytes'] = int(_peak(lambda: path_b(False)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -493,12 +618,17 @@ def main():
     ap.add_argument('--segmented', action='store_true')
     ap.add_argument('--exclude', action='store_true')
     ap.add_argument('--rank', action='store_true')
+    ap.add_argument('--cmc', action='store_true')
     ap.add_argument('--parent-lib', default=None)
     a = ap.parse_args()
     from pps_amd import ops
     for name in [s for s in a.shapes.split(',') if s]:
         Q, G, D, k = SHAPES[name]
-        if a.rank:
+        if a.cmc:
+            for features in ('gaussian', 'clustered'):
+                print(json.dumps(bench_cmc(name, Q, G, D, a.reps, ops, features)), flush=True)
+                torch.cuda.empty_cache()
+        elif a.rank:
             for features in ('gaussian', 'clustered'):
                 print(json.dumps(bench_rank(name, Q, G, D, a.reps, ops, features)), flush=True)
                 torch.cuda.empty_cache()
