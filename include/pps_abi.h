@@ -616,6 +616,73 @@ int pps_re_ranking_ld(const float* q_g, int64_t ld_qg, const float* q_q, int64_t
                       double lambda_value, int flags, void* workspace, int64_t ws_bytes,
                       float* out, void* stream);
 
+/* pps_search_h2_tiled that also returns every query's largest squared
+ * distance: rowmax [Q] has the bits of max_c fl(d[r][c] * d[r][c]) over the G
+ * real columns of the matrix pps_distmat_h2_tiled would write (padded columns
+ * of the last tile never count; zeros when G == 0).  vals / idx, every other
+ * argument, check and the workspace are pps_search_h2_tiled's.  The entry
+ * zeroes rowmax on the stream; the kernel folds each pass's maximum in with
+ * one atomic max on the float bits per row, so segments need no extra merge. */
+int pps_search_h2_tiled_rowmax(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                               const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                               int D, int metric, int k, int segments, int tile,
+                               void* workspace, int64_t ws_bytes,
+                               float* vals, int32_t* idx, float* rowmax, void* stream);
+
+/* Distances of listed pairs from the f16x2 planes: out[r][t] = the distance
+ * of a-row r to b-row lists[r][t] for t < min(counts[r], cap), each with the
+ * bits pps_distmat_h2_tiled would write at that cell; cells past a row's
+ * count are left as they are.  lists / out are [Q][cap] int32 / float32
+ * DEVICE arrays, counts [Q] (null = cap entries in every row); an index
+ * outside [0, G) is read as the nearest valid row.  Operands (q2t .. D,
+ * metric) and their checks are pps_search_h2_tiled's; cap >= 1; G > 0 unless
+ * Q == 0. */
+int pps_pair_dist_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                     const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
+                     int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
+                     void* stream);
+
+/* Row-form k-reciprocal re-ranking: no buffer grows with N^2 (N = Q + G) and
+ * G has no cap.  W[i][j] = the value pps_distmat_h2_tiled writes for a-row
+ * x_i and b-row x_j of x = [queries; gallery]; rowmax[i] = max_j
+ * fl(W[i][j]^2); OD(i, j) = fl(W[i][j]^2) / rowmax[i]; the initial rank of
+ * row i is its stable (W[i][j], j) top-(k1 + 1); the reciprocal sets, their
+ * expansion, the weights, V_qe, the Jaccard sums and the blend are
+ * pps_re_ranking's, operand order included.  On an exactly symmetric W this
+ * is the reference's formula.  out [Q][G].
+ *  - pps_re_ranking_rows: the materialised twin, from W [N][ldw] (DEVICE,
+ *    ldw >= N): pps_topk on W's rows, the row maxima and every weight and
+ *    blend operand read from W.
+ *  - pps_re_ranking_features: from the planes of x (x2t / xsq / xrs, N rows,
+ *    pps_split_f16x2_sqnorm_tiled) and of the gallery rows alone (g2t / gsq /
+ *    grs, G rows: the tiled layout cannot address rows Q.. of x as an
+ *    operand of their own unless Q % 16 == 0).  The ranks and maxima come
+ *    from pps_search_h2_tiled_rowmax of x against x, the weights' distances
+ *    from pps_pair_dist_h2, and the q x g block is written into out by the
+ *    distance kernel and blended in place.  Bit for bit the twin's result on
+ *    the W those planes give.  segments / tile: pps_search_h2_tiled's.
+ * g_window: gallery rows one Jaccard workgroup keeps in LDS; 0 = one window
+ * when G <= 38400, else equal windows of at most 38400 rows; a positive value
+ * (<= 38400) forces the size -- every size gives the same bits.
+ * Checks, all before anything is launched: Q, G > 0; N < 2^31; N >= k1 + 1;
+ * k1 + 1 <= 64 and <= pps_search_max_k(); 1 <= k2 <= k1 + 1; (features)
+ * D % 32 == 0, known metric, x's planes under 2 GiB, 16-byte aligned planes;
+ * a 256-byte aligned workspace.  N * k2 * (V row capacity) >= 2^31 and a
+ * workspace smaller than the size function's value are PPS_ERR_CAPACITY.
+ * The size functions are host arithmetic, non-decreasing in G, -1 on bad
+ * arguments; the features one includes the search's workspace.  Everything
+ * runs on the one stream without host synchronisation. */
+int64_t pps_rerank_rows_workspace_bytes(int64_t Q, int64_t G, int k1, int k2);
+int pps_re_ranking_rows(const float* W, int64_t ldw, int64_t Q, int64_t G, int k1, int k2,
+                        double lambda_value, int64_t g_window, void* workspace, int64_t ws_bytes,
+                        float* out, void* stream);
+int64_t pps_rerank_features_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments);
+int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* xrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t Q,
+                            int64_t G, int D, int metric, int k1, int k2, double lambda_value,
+                            int segments, int tile, int64_t g_window, void* workspace,
+                            int64_t ws_bytes, float* out, void* stream);
+
 /* ---- feature extractor ----------------------------------------------------
  * Implicit-GEMM convolution + test-mode SpatialBN + optional residual Sum +
  * optional ReLU, fused (ResNet.py:246-256 stem conv, :276-333 bottleneck,

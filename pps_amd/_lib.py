@@ -105,6 +105,16 @@ SIGNATURES = {
     'pps_cmc_count_h2_tiled': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
                                c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
                                c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr],
+    'pps_search_h2_tiled_rowmax': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                                   c_int, c_int, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                   c_ptr],
+    'pps_pair_dist_h2': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
+                         c_ptr, c_ptr, c_int, c_ptr, c_ptr],
+    'pps_re_ranking_rows': [c_ptr, c_i64, c_i64, c_i64, c_int, c_int, ctypes.c_double, c_i64,
+                            c_ptr, c_i64, c_ptr, c_ptr],
+    'pps_re_ranking_features': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int,
+                                c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_i64, c_ptr,
+                                c_i64, c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],
@@ -206,6 +216,8 @@ EXTRA = {
     'pps_rerank_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
     'pps_rerank_workspace_bytes_ld': ([c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_int,
                                        c_int, c_int], ctypes.c_int64),
+    'pps_rerank_rows_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
+    'pps_rerank_features_workspace_bytes': ([c_i64, c_i64, c_int, c_int, c_int], ctypes.c_int64),
     'pps_last_error': ([], ctypes.c_char_p),
     'pps_registered_ops': ([], ctypes.c_char_p),
     'pps_model_feat_dim': ([c_ptr], ctypes.c_int),

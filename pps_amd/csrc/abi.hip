@@ -501,6 +501,83 @@ int pps_re_ranking(const float* q_g, const float* q_q, const float* g_g, int64_t
                               ws_bytes, out, stream);
 }
 
+// the (k1, k2, g_window, size) checks the two row-form entries share; every one
+// runs before anything is launched
+static int rerank_rows_guards(const char* fn, int64_t Q, int64_t G, int k1, int k2,
+                              int64_t g_window) {
+  PPS_ENFORCE(Q > 0 && G > 0, "bad shape");
+  PPS_ENFORCE(Q + G < (1ll << 31), "N = Q + G must fit int32");
+  PPS_ENFORCE(k1 >= 1 && k1 + 1 <= 64 && k1 + 1 <= kTkwMaxK,
+              "k1 + 1 must be <= 64 and <= pps_search_max_k()");
+  PPS_ENFORCE(k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
+  const int K1 = k1 + 1, Kh = (int)lrint(k1 / 2.0) + 1;
+  PPS_ENFORCE(K1 + K1 * Kh <= 1024, "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
+  const int vcap = K1 + K1 * Kh <= 256 ? 256 : (K1 + K1 * Kh <= 512 ? 512 : 1024);
+  PPS_ENFORCE(k2 * vcap <= 4096, "k2 * V row capacity must be <= 4096");
+  PPS_ENFORCE((Q + G) >= K1, "need Q + G >= k1 + 1");
+  PPS_ENFORCE(g_window >= 0 && g_window <= kJacMaxWindow,
+              "g_window must be in [0, " + std::to_string(kJacMaxWindow) + "] (0 = auto)");
+  PPS_ENFORCE(g_window == 0 || (G + g_window - 1) / g_window <= 65535,
+              "more than 65535 gallery windows");
+  if ((Q + G) * (int64_t)(k2 * vcap) >= (1ll << 31)) {
+    set_error(std::string(fn) + ": N * qcap = " + std::to_string(Q + G) + " * " +
+              std::to_string(k2 * vcap) + " entries of the inverted index do not fit int32");
+    return PPS_ERR_CAPACITY;
+  }
+  return PPS_OK;
+}
+
+int64_t pps_rerank_rows_workspace_bytes(int64_t Q, int64_t G, int k1, int k2) {
+  if (Q < 0 || G < 0 || k1 < 1 || k1 + 1 > 64 || k2 < 1 || k2 > k1 + 1) return -1;
+  return rerank_rows_workspace_bytes(false, Q, G, k1, k2, 0);
+}
+
+int pps_re_ranking_rows(const float* W, int64_t ldw, int64_t Q, int64_t G, int k1, int k2,
+                        double lambda_value, int64_t g_window, void* workspace, int64_t ws_bytes,
+                        float* out, void* stream) {
+  PPS_ENFORCE(W && workspace && out, "null pointer");
+  const int rc = rerank_rows_guards("pps_re_ranking_rows", Q, G, k1, k2, g_window);
+  if (rc != PPS_OK) return rc;
+  PPS_ENFORCE(ldw >= Q + G, "ldw smaller than the rows");
+  PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RrRows src{};
+  src.W = W;
+  src.ldw = ldw;
+  return rerank_rows(src, Q, G, k1, k2, lambda_value, g_window, workspace,
+                     ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
+}
+
+int64_t pps_rerank_features_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments) {
+  if (Q < 0 || G < 0 || k1 < 1 || k1 + 1 > 64 || k1 + 1 > kTkwMaxK || k2 < 1 || k2 > k1 + 1 ||
+      segments < 0)
+    return -1;
+  return rerank_rows_workspace_bytes(true, Q, G, k1, k2, segments);
+}
+
+int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* xrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t Q,
+                            int64_t G, int D, int metric, int k1, int k2, double lambda_value,
+                            int segments, int tile, int64_t g_window, void* workspace,
+                            int64_t ws_bytes, float* out, void* stream) {
+  PPS_ENFORCE(x2t && xsq && xrs && g2t && gsq && grs && workspace && out, "null pointer");
+  PPS_ENFORCE(D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
+  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
+  const int rc = rerank_rows_guards("pps_re_ranking_features", Q, G, k1, k2, g_window);
+  if (rc != PPS_OK) return rc;
+  PPS_ENFORCE(2 * ((Q + G + 15) / 16 * 16) * D * 2 < kMaxBufBytes, "planes over 2 GiB");
+  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
+  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
+              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
+  PPS_ENFORCE(aligned16(x2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RrRows src{};
+  src.x2t = x2t; src.xsq = xsq; src.xrs = xrs;
+  src.g2t = g2t; src.gsq = gsq; src.grs = grs;
+  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
+  return rerank_rows(src, Q, G, k1, k2, lambda_value, g_window, workspace,
+                     ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
+}
+
 int pps_conv1x1_seam_x3(const float* x, int64_t M, int K1, const uint16_t* w2c, int N1,
                         const float* scale2c, const float* shift2c, const float* residual,
                         float* trunk, const uint16_t* w2a, int N2, const float* scale2a,

@@ -77,10 +77,7 @@ struct PairArgs {
   float* junk_d; int32_t* junk_idx; int32_t* junk_cnt;
 };
 
-// byte offset of row r's chunk 0, slot s within a plane: [r / 16][kc][r % 16][32]
-__device__ inline int64_t h2_frag_off(int r, int nkc, int slot) {
-  return (int64_t)(r >> 4) * nkc * 1024 + (r & 15) * 64 + slot * 16;
-}
+// h2_frag_off (a row's fragment in a chunk-tiled plane): retrieval.hpp
 
 __global__ void __launch_bounds__(64 * kPairWaves)
 collect_matches_h2_kernel(PairArgs a) {

@@ -17,6 +17,12 @@
 //  4. rerank_vqe     : V_qe[i] = mean of V rows initial_rank[i,:k2] (:490-494)
 //  5. rerank_csc_*   : inverted index of V_qe                     (:497-499)
 //  6. rerank_jaccard : temp_min, jaccard, lambda blend, [Q][G] out (:501-518)
+//
+// Row form (rerank_rows): OD(i, j) = W[i][j]^2 / max_j W[i][j]^2
+// with W the general h2 kernel's matrix, never built on the features path --
+// steps 1-2 are the fused search with row maxima, step 3 is split into lists /
+// pair distances / weights, 4-5 run unchanged, 6 blends the q x g block in place
+// over gallery windows (no N x N buffer, no cap on G).
 #include <vector>
 
 #include "retrieval.hpp"
@@ -291,7 +297,11 @@ struct VRowsLds {
   size_t bytes() const { return sizeof(int32_t) * (size_t)(E2 + tab); }
 };
 
-template <bool OTF>
+// MODE: where the weights' OD comes from -- the dense buffer, M in place, or
+// (kVLists, the row-form path) nowhere: the kernel stops where uq is complete
+// and writes the unique expansion list; rerank_v_weights_kernel finishes the row
+constexpr int kVDense = 0, kVOtf = 1, kVLists = 2;
+template <int MODE>
 __global__ void __launch_bounds__(64)
 rerank_v_rows_kernel(const float* __restrict__ od, int64_t N, int64_t ldo,
                      const int32_t* __restrict__ rank, int K1, int Kh, int vcap, int E2,
@@ -374,8 +384,14 @@ rerank_v_rows_kernel(const float* __restrict__ od, int64_t N, int64_t ldo,
     u += __popcll(fb);
   }
   __syncthreads();
+  if constexpr (MODE == kVLists) {
+    for (int t = lane; t < min(u, vcap); t += 64) v_idx[i * vcap + t] = uq[t];
+    if (lane == 0) v_cnt[i] = u;
+    return;
+  }
   // weight = exp(-OD[i, idx]); V = weight / np.sum(weight) (float32, index order)
-  for (int t = lane; t < u; t += 64) wv[t] = expf(-od_at<OTF>(od, ldo, M, i, uq[t]));
+  for (int t = lane; t < u; t += 64)
+    wv[t] = expf(-od_at<MODE == kVOtf>(od, ldo, M, i, uq[t]));
   __syncthreads();
   float wsum = lane == 0 ? np_pairwise_sum<4>(wv, u) : 0.f;
   wsum = __shfl(wsum, 0);
@@ -385,6 +401,35 @@ rerank_v_rows_kernel(const float* __restrict__ od, int64_t N, int64_t ldo,
     v_val[i * vcap + t] = wv[t] / wsum;
   }
   if (lane == 0) v_cnt[i] = u;
+}
+
+// Row form, twin: m[i][t] = W[i][v_idx[i][t]] into v_val (the features path
+// gets the same cells from pair_dist_h2)
+__global__ void __launch_bounds__(64)
+rerank_gather_w_kernel(const float* __restrict__ W, int64_t ldw,
+                       const int32_t* __restrict__ v_idx, const int32_t* __restrict__ v_cnt,
+                       int vcap, float* __restrict__ v_val) {
+  const int64_t i = blockIdx.x;
+  const int u = min(v_cnt[i], vcap);
+  for (int t = threadIdx.x; t < u; t += 64) v_val[i * vcap + t] = W[i * ldw + v_idx[i * vcap + t]];
+}
+
+// Row form: the tail of rerank_v_rows_kernel on m[i][t] (in v_val, overwritten):
+// weight = exp(-rr_od(m, rowmax[i])); V = weight / np.sum(weight)
+constexpr int kVWeightsCap = 1024;   // the largest V row (RrLayout::vcap)
+__global__ void __launch_bounds__(64)
+rerank_v_weights_kernel(const float* __restrict__ rowmax, const int32_t* __restrict__ v_cnt,
+                        int vcap, float* __restrict__ v_val) {
+  __shared__ float wv[kVWeightsCap];
+  const int64_t i = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int u = min(v_cnt[i], vcap);
+  const float cm = rowmax[i];
+  for (int t = lane; t < u; t += 64) wv[t] = expf(-rr_od(v_val[i * vcap + t], cm));
+  __syncthreads();
+  float wsum = lane == 0 ? np_pairwise_sum<4>(wv, u) : 0.f;
+  wsum = __shfl(wsum, 0);
+  for (int t = lane; t < u; t += 64) v_val[i * vcap + t] = wv[t] / wsum;
 }
 
 // ---- 4) V_qe rows: mean of k2 sparse rows (row order = initial_rank order) ----
@@ -690,27 +735,44 @@ __global__ void rerank_csc_fill_kernel(int64_t N, const int32_t* __restrict__ q_
 constexpr int kJacThreads = 1024;
 constexpr int kJacCols = 128;    // column metadata loaded per batch
 constexpr int kJacStage = 1024;  // staged (row, value) entries
+// A block takes the gallery window [w0, w1) = blockIdx.y's wsize rows (grid =
+// (Q, windows); one window of G rows unless G is past kJacMaxWindow): staged
+// entries outside it are skipped and tm is indexed from w0, so each tm[j]
+// still receives the same terms in the same column order -- any window size
+// gives the bits of one window.
+// MODE: the blend's OD from the dense buffer, from M in place, or (kJacRows,
+// the row form) from out itself: out[i][g] holds W[i][Q + g] on entry and the
+// thread that reads a cell overwrites it with the blend (M.colmax = rowmax).
+constexpr int kJacDense = 0, kJacOtf = 1, kJacRows = 2;
 size_t jaccard_lds_bytes(int64_t G) {
   return sizeof(float) * (size_t)G + (sizeof(int32_t) + sizeof(float)) * kJacStage;
 }
-template <bool OTF>
+// the matrix modes write a buffer nothing else reads; the row form reads out itself
+template <int MODE> struct JacOut { using type = float* __restrict__; };
+template <> struct JacOut<kJacRows> { using type = float*; };
+template <int MODE>
 __global__ void __launch_bounds__(kJacThreads)
 rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_t ldo,
                       RrMatrix M, const int32_t* __restrict__ q_idx,
                       const float* __restrict__ q_val, const int32_t* __restrict__ q_cnt,
                       int qcap, const int32_t* __restrict__ start,
                       const int32_t* __restrict__ csc_row, const float* __restrict__ csc_val,
-                      float lam, float one_m_lam, float* __restrict__ out) {
-  extern __shared__ float tm[];  // [G] temp_min of the gallery rows, then the stage
+                      float lam, float one_m_lam, typename JacOut<MODE>::type out,
+                      int64_t wsize) {
+  extern __shared__ float tm[];  // [wsize] temp_min of the window's gallery rows, then the stage
   const int64_t G = N - Q;
-  int32_t* srow = reinterpret_cast<int32_t*>(tm + G);
+  // only the row form launches several windows: the matrix modes' window is
+  // [0, G) at compile time and their loops are the one-window code
+  constexpr bool WIN = MODE == kJacRows;
+  const int64_t w0 = WIN ? blockIdx.y * wsize : 0, w1 = WIN ? min(G, w0 + wsize) : G;
+  int32_t* srow = reinterpret_cast<int32_t*>(tm + wsize);
   float* sval = reinterpret_cast<float*>(srow + kJacStage);
   __shared__ int m_off[kJacCols + 1], m_s0[kJacCols];
   __shared__ float m_a[kJacCols];
   __shared__ int s_wtot;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t i = blockIdx.x;
-  for (int64_t j = tid; j < G; j += kJacThreads) tm[j] = 0.f;
+  for (int64_t j = tid; j < w1 - w0; j += kJacThreads) tm[j] = 0.f;
   const int c = min(q_cnt[i], qcap);
   for (int e0 = 0; e0 < c; e0 += kJacCols) {
     const int nb = min(kJacCols, c - e0);
@@ -755,8 +817,8 @@ rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_
         const float av = m_a[ca];
         const int s0 = m_s0[ca], s1 = s0 + (m_off[ca + 1] - m_off[ca]);
         for (int s = s0 + tid; s < s1; s += kJacThreads) {
-          const int64_t r = csc_row[s] - Q;
-          if (r >= 0) tm[r] = tm[r] + fminf(av, csc_val[s]);
+          const int64_t r = csc_row[s] - Q - w0;
+          if (r >= 0 && (!WIN || r < w1 - w0)) tm[r] = tm[r] + fminf(av, csc_val[s]);
         }
         __syncthreads();
         ++ca;
@@ -777,8 +839,8 @@ rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_
       for (int k = ca; k < cb; ++k) {   // column order
         const float av = m_a[k];
         for (int f = m_off[k] - base + tid; f < m_off[k + 1] - base; f += kJacThreads) {
-          const int64_t r = srow[f] - Q;
-          if (r >= 0) tm[r] = tm[r] + fminf(av, sval[f]);   // one row per column entry
+          const int64_t r = srow[f] - Q - w0;   // one row per column entry
+          if (r >= 0 && (!WIN || r < w1 - w0)) tm[r] = tm[r] + fminf(av, sval[f]);
         }
         __syncthreads();
       }
@@ -786,12 +848,15 @@ rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_
     }
   }
   __syncthreads();
-  for (int64_t j = Q + tid; j < N; j += kJacThreads) {
-    const float t = tm[j - Q];
+  for (int64_t j = Q + w0 + tid; j < Q + w1; j += kJacThreads) {
+    const float t = tm[j - Q - w0];
     const float jac = 1.f - t / (2.f - t);
     const float wj = jac * one_m_lam;                          // rounded
-    const float wo = od_at<OTF>(od, ldo, M, i, j) * lam;       // rounded
-    out[i * (N - Q) + (j - Q)] = wj + wo;
+    float o;
+    if constexpr (MODE == kJacRows) o = rr_od(out[i * G + (j - Q)], M.colmax[i]);
+    else o = od_at<MODE == kJacOtf>(od, ldo, M, i, j);
+    const float wo = o * lam;                                  // rounded
+    out[i * G + (j - Q)] = wj + wo;
   }
 }
 
@@ -840,6 +905,54 @@ static size_t rr_rest_bytes(int64_t Q, int64_t G, int k1, int k2) {
   s += r(4 * N * qcap) * 2 + r(4 * N) + r(4 * (N + 1)) * 3 + r(4 * N * qcap) * 2;
   s += r(4 * N) + r(4);   // V_qe overflow rows + count
   return s;
+}
+
+// The sparse per-row structures of a call (workspace carves)
+struct RrSparse {
+  int32_t* rank;
+  int32_t* v_idx; float* v_val; int32_t* v_cnt;
+  int32_t* q_idx; float* q_val; int32_t* q_cnt;
+  int32_t* col_cnt; int32_t* start; int32_t* fill;
+  int32_t* csc_row; float* csc_val;
+  int32_t* ovf_rows; int32_t* ovf_n;
+};
+
+// Stages 4 and 5 (V_qe and its inverted index) from the finished V rows
+static int rr_vqe_csc(int64_t N, const RrLayout& L, int k2, const RrSparse& sp, hipStream_t st) {
+  const int K1 = L.K1, vcap = L.vcap, qcap = L.qcap;
+  int32_t *rank = sp.rank, *v_idx = sp.v_idx, *v_cnt = sp.v_cnt, *q_idx = sp.q_idx;
+  int32_t *q_cnt = sp.q_cnt, *col_cnt = sp.col_cnt, *start = sp.start, *fill = sp.fill;
+  int32_t *csc_row = sp.csc_row, *ovf_rows = sp.ovf_rows, *ovf_n = sp.ovf_n;
+  float *v_val = sp.v_val, *q_val = sp.q_val, *csc_val = sp.csc_val;
+  const int qc = k2 != 1 ? qcap : vcap;
+  // the V_qe kernels also count the inverted index's column sizes
+  (void)hipMemsetAsync(col_cnt, 0, sizeof(int32_t) * (N + 1), st);
+  if (k2 != 1) {
+    (void)hipMemsetAsync(ovf_n, 0, sizeof(int32_t), st);
+    hipLaunchKernelGGL(rerank_vqe_wave_kernel, dim3((unsigned)N), dim3(64), 0, st, N, rank, K1,
+                       k2, v_idx, v_val, v_cnt, vcap, qcap, q_idx, q_val, q_cnt, col_cnt,
+                       ovf_rows, ovf_n);
+    PPS_CHECK_LAUNCH_S("rerank_vqe_wave_kernel", st);
+    hipLaunchKernelGGL(rerank_vqe_kernel, dim3(256), dim3(256), 0, st, N, rank, K1, k2, v_idx,
+                       v_val, v_cnt, vcap, qcap, q_idx, q_val, q_cnt, col_cnt, ovf_rows, ovf_n);
+    PPS_CHECK_LAUNCH_S("rerank_vqe_kernel", st);
+  } else {
+    (void)hipMemcpyAsync(q_idx, v_idx, sizeof(int32_t) * N * vcap, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(q_val, v_val, sizeof(float) * N * vcap, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(q_cnt, v_cnt, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st);
+  }
+  (void)hipMemsetAsync(fill, 0, sizeof(int32_t) * (N + 1), st);
+  if (k2 == 1) {   // V_qe = V: count here
+    hipLaunchKernelGGL(rerank_csc_count_kernel, dim3((unsigned)N), dim3(256), 0, st, N, q_idx,
+                       q_val, q_cnt, qc, col_cnt);
+    PPS_CHECK_LAUNCH_S("rerank_csc_count_kernel", st);
+  }
+  hipLaunchKernelGGL(rerank_scan_kernel, dim3(1), dim3(1024), 0, st, N, col_cnt, start);
+  PPS_CHECK_LAUNCH_S("rerank_scan_kernel", st);
+  hipLaunchKernelGGL(rerank_csc_fill_kernel, dim3((unsigned)N), dim3(256), 0, st, N, q_idx,
+                     q_val, q_cnt, qc, start, fill, csc_row, csc_val);
+  PPS_CHECK_LAUNCH_S("rerank_csc_fill_kernel", st);
+  return PPS_OK;
 }
 
 int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const float* gg,
@@ -956,49 +1069,26 @@ int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const f
   }
   const VRowsLds vl(K1, Kh);
   if (inplace)
-    hipLaunchKernelGGL(rerank_v_rows_kernel<true>, dim3((unsigned)N), dim3(64), vl.bytes(), st, od,
+    hipLaunchKernelGGL(rerank_v_rows_kernel<kVOtf>, dim3((unsigned)N), dim3(64), vl.bytes(), st, od,
                        N, ldo, rank, K1, Kh, vcap, vl.E2, v_idx, v_val, v_cnt, M);
   else
-    hipLaunchKernelGGL(rerank_v_rows_kernel<false>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
+    hipLaunchKernelGGL(rerank_v_rows_kernel<kVDense>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
                        od, N, ldo, rank, K1, Kh, vcap, vl.E2, v_idx, v_val, v_cnt, M);
   PPS_CHECK_LAUNCH_S("rerank_v_rows_kernel", st);
-  // the V_qe kernels also count the inverted index's column sizes
-  (void)hipMemsetAsync(col_cnt, 0, sizeof(int32_t) * (N + 1), st);
-  if (k2 != 1) {
-    (void)hipMemsetAsync(ovf_n, 0, sizeof(int32_t), st);
-    hipLaunchKernelGGL(rerank_vqe_wave_kernel, dim3((unsigned)N), dim3(64), 0, st, N, rank, K1,
-                       k2, v_idx, v_val, v_cnt, vcap, qcap, q_idx, q_val, q_cnt, col_cnt,
-                       ovf_rows, ovf_n);
-    PPS_CHECK_LAUNCH_S("rerank_vqe_wave_kernel", st);
-    hipLaunchKernelGGL(rerank_vqe_kernel, dim3(256), dim3(256), 0, st, N, rank, K1, k2, v_idx,
-                       v_val, v_cnt, vcap, qcap, q_idx, q_val, q_cnt, col_cnt, ovf_rows, ovf_n);
-    PPS_CHECK_LAUNCH_S("rerank_vqe_kernel", st);
-  } else {
-    (void)hipMemcpyAsync(q_idx, v_idx, sizeof(int32_t) * N * vcap, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(q_val, v_val, sizeof(float) * N * vcap, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(q_cnt, v_cnt, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, st);
-  }
   const int qc = k2 != 1 ? qcap : vcap;
-  (void)hipMemsetAsync(fill, 0, sizeof(int32_t) * (N + 1), st);
-  if (k2 == 1) {   // V_qe = V: count here
-    hipLaunchKernelGGL(rerank_csc_count_kernel, dim3((unsigned)N), dim3(256), 0, st, N, q_idx,
-                       q_val, q_cnt, qc, col_cnt);
-    PPS_CHECK_LAUNCH_S("rerank_csc_count_kernel", st);
-  }
-  hipLaunchKernelGGL(rerank_scan_kernel, dim3(1), dim3(1024), 0, st, N, col_cnt, start);
-  PPS_CHECK_LAUNCH_S("rerank_scan_kernel", st);
-  hipLaunchKernelGGL(rerank_csc_fill_kernel, dim3((unsigned)N), dim3(256), 0, st, N, q_idx,
-                     q_val, q_cnt, qc, start, fill, csc_row, csc_val);
-  PPS_CHECK_LAUNCH_S("rerank_csc_fill_kernel", st);
+  const RrSparse sp{rank, v_idx, v_val, v_cnt, q_idx, q_val, q_cnt, col_cnt, start, fill,
+                    csc_row, csc_val, ovf_rows, ovf_n};
+  const int src = rr_vqe_csc(N, L, k2, sp, st);
+  if (src != PPS_OK) return src;
   const size_t jac_lds = jaccard_lds_bytes(G);
   if (inplace)
-    hipLaunchKernelGGL(rerank_jaccard_kernel<true>, dim3((unsigned)Q), dim3(kJacThreads), jac_lds,
-                       st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row, csc_val, lam,
-                       one_m_lam, out);
+    hipLaunchKernelGGL(rerank_jaccard_kernel<kJacOtf>, dim3((unsigned)Q), dim3(kJacThreads),
+                       jac_lds, st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row,
+                       csc_val, lam, one_m_lam, out, G);
   else
-    hipLaunchKernelGGL(rerank_jaccard_kernel<false>, dim3((unsigned)Q), dim3(kJacThreads), jac_lds,
-                       st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row, csc_val, lam,
-                       one_m_lam, out);
+    hipLaunchKernelGGL(rerank_jaccard_kernel<kJacDense>, dim3((unsigned)Q), dim3(kJacThreads),
+                       jac_lds, st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row,
+                       csc_val, lam, one_m_lam, out, G);
   PPS_CHECK_LAUNCH_S("rerank_jaccard_kernel", st);
   return PPS_OK;
 }
@@ -1016,6 +1106,136 @@ size_t rerank_workspace_bytes_for(const float* qg, int64_t ldqg, const float* qq
   const bool inplace = rr_inplace(qg, ldqg, qq, ldqq, gg, ldgg, Q, G, k1 + 1, flags, od_probe);
   const size_t odb = rr_od_bytes(inplace, (flags & PPS_RERANK_WHOLE) != 0, Q, G, k1 + 1);
   return (odb + 255) / 256 * 256 + rr_rest_bytes(Q, G, k1, k2);
+}
+
+// ---- row form --------------------------------------------------
+// The carves of a row-form call: everything is per row of x (about 27 KB at
+// k1 = 20, k2 = 6), plus the fused search's workspace on the features path --
+// nothing grows with N^2.
+struct RrRowsCarve {
+  size_t rowmax, topv, rank, v_idx, v_val, v_cnt, q_idx, q_val, q_cnt, col_cnt, start, fill,
+      csc_row, csc_val, ovf_rows, ovf_n, search, total;
+  int64_t search_bytes;
+  RrRowsCarve(bool features, int64_t Q, int64_t G, int k1, int k2, int segments) {
+    const int64_t N = Q + G;
+    const RrLayout L(k1, k2);
+    const size_t K1 = L.K1, vcap = L.vcap, qcap = L.qcap;
+    size_t p = 0;
+    auto take = [&](size_t bytes) {
+      const size_t r = p;
+      p += (bytes + 255) / 256 * 256;
+      return r;
+    };
+    rowmax = take(4 * N);
+    topv = take(4 * N * K1);
+    rank = take(4 * N * K1);
+    v_idx = take(4 * N * vcap);
+    v_val = take(4 * N * vcap);
+    v_cnt = take(4 * N);
+    q_idx = take(4 * N * qcap);
+    q_val = take(4 * N * qcap);
+    q_cnt = take(4 * N);
+    col_cnt = take(4 * (N + 1));
+    start = take(4 * (N + 1));
+    fill = take(4 * (N + 1));
+    csc_row = take(4 * N * qcap);
+    csc_val = take(4 * N * qcap);
+    ovf_rows = take(4 * N);
+    ovf_n = take(4);
+    search_bytes = features ? search_h2_self_workspace_bound(N, L.K1, segments) : 0;
+    search = take((size_t)search_bytes);
+    total = p;
+  }
+};
+
+int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1, int k2,
+                                    int segments) {
+  return (int64_t)RrRowsCarve(features, Q, G, k1, k2, segments).total;
+}
+
+int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
+                int64_t g_window, void* ws, size_t ws_bytes, float* out, hipStream_t st) {
+  const float lam = (float)lambda, one_m_lam = (float)(1.0 - lambda);
+  const int64_t N = Q + G;
+  const RrLayout L(k1, k2);
+  const int K1 = L.K1, Kh = L.Kh, vcap = L.vcap;
+  const bool features = src.W == nullptr;
+  const RrRowsCarve C(features, Q, G, k1, k2, src.segments);
+  if (C.total > ws_bytes) {
+    set_error("row-form rerank workspace too small: need " + std::to_string(C.total) + " bytes");
+    return PPS_ERR_CAPACITY;
+  }
+  char* base = reinterpret_cast<char*>(ws);
+  auto f32 = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+  auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
+  float* rowmax = f32(C.rowmax);
+  float* topv = f32(C.topv);
+  const RrSparse sp{i32(C.rank), i32(C.v_idx), f32(C.v_val), i32(C.v_cnt), i32(C.q_idx),
+                    f32(C.q_val), i32(C.q_cnt), i32(C.col_cnt), i32(C.start), i32(C.fill),
+                    i32(C.csc_row), f32(C.csc_val), i32(C.ovf_rows), i32(C.ovf_n)};
+  // 1-2) rowmax[i] = max_j fl(W[i][j]^2) and the stable (W[i][j], j) top-(k1+1)
+  if (features) {
+    const int rc = search_h2_tiled("pps_re_ranking_features", false, src.x2t, N, src.xsq, src.xrs,
+                                   src.x2t, src.xsq, src.xrs, N, src.D, src.metric, K1,
+                                   src.segments, src.tile, base + C.search, C.search_bytes, topv,
+                                   sp.rank, nullptr, nullptr, rowmax, st);
+    if (rc != PPS_OK) return rc;
+  } else {
+    (void)hipMemsetAsync(rowmax, 0, sizeof(float) * N, st);
+    hipLaunchKernelGGL(rerank_rowmax_sq_kernel, dim3((unsigned)N), dim3(256), 0, st, src.W, N,
+                       src.ldw, reinterpret_cast<unsigned*>(rowmax));
+    PPS_CHECK_LAUNCH_S("rerank_rowmax_sq_kernel", st);
+    const int rc = topk(src.W, N, N, src.ldw, K1, topv, sp.rank, st);
+    if (rc != PPS_OK) return rc;
+  }
+  // 3) the unique expansion lists, their distances m[i][t], the weights
+  const VRowsLds vl(K1, Kh);
+  const RrMatrix none{};
+  hipLaunchKernelGGL(rerank_v_rows_kernel<kVLists>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
+                     (const float*)nullptr, N, (int64_t)0, sp.rank, K1, Kh, vcap, vl.E2, sp.v_idx,
+                     sp.v_val, sp.v_cnt, none);
+  PPS_CHECK_LAUNCH_S("rerank_v_rows_kernel", st);
+  if (features) {
+    const int rc = pair_dist_h2(src.x2t, N, N, src.xsq, src.xrs, src.x2t, src.xsq, src.xrs, N,
+                                src.D, src.metric, sp.v_idx, sp.v_cnt, vcap, sp.v_val, st);
+    if (rc != PPS_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(rerank_gather_w_kernel, dim3((unsigned)N), dim3(64), 0, st, src.W, src.ldw,
+                       sp.v_idx, sp.v_cnt, vcap, sp.v_val);
+    PPS_CHECK_LAUNCH_S("rerank_gather_w_kernel", st);
+  }
+  hipLaunchKernelGGL(rerank_v_weights_kernel, dim3((unsigned)N), dim3(64), 0, st, rowmax, sp.v_cnt,
+                     vcap, sp.v_val);
+  PPS_CHECK_LAUNCH_S("rerank_v_weights_kernel", st);
+  // 4-5) unchanged
+  const int rc45 = rr_vqe_csc(N, L, k2, sp, st);
+  if (rc45 != PPS_OK) return rc45;
+  // 6) out = the q x g block W[i][Q + g]; the Jaccard pass blends it in place
+  if (features) {
+    const int rc = distmat_h2_head(src.x2t, Q, N, src.xsq, src.xrs, src.g2t, src.gsq, src.grs, G,
+                                   src.D, src.metric, out, G, st);
+    if (rc != PPS_OK) return rc;
+  } else {
+    (void)hipMemcpy2DAsync(out, sizeof(float) * G, src.W + Q, sizeof(float) * src.ldw,
+                           sizeof(float) * G, Q, hipMemcpyDeviceToDevice, st);
+  }
+  // windows: one when the gallery fits, else equal ones of at most kJacMaxWindow rows
+  int64_t wsize = g_window;
+  if (wsize <= 0) {
+    const int64_t nw = (G + kJacMaxWindow - 1) / kJacMaxWindow;
+    wsize = (G + nw - 1) / nw;
+  }
+  if (wsize > G) wsize = G;
+  const int64_t nwin = (G + wsize - 1) / wsize;
+  RrMatrix M{};
+  M.colmax = rowmax;
+  const int qc = k2 != 1 ? L.qcap : vcap;
+  hipLaunchKernelGGL(rerank_jaccard_kernel<kJacRows>, dim3((unsigned)Q, (unsigned)nwin),
+                     dim3(kJacThreads), jaccard_lds_bytes(wsize), st, Q, N, (const float*)nullptr,
+                     (int64_t)0, M, sp.q_idx, sp.q_val, sp.q_cnt, qc, sp.start, sp.csc_row,
+                     sp.csc_val, lam, one_m_lam, out, wsize);
+  PPS_CHECK_LAUNCH_S("rerank_jaccard_kernel", st);
+  return PPS_OK;
 }
 
 }  // namespace pps

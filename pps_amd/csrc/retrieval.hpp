@@ -63,6 +63,35 @@ inline int64_t fused_segments(int64_t Q, int64_t G, int segments, int BM, int BN
   return S < tiles_n ? S : tiles_n;
 }
 
+// ---- fused f16x2 entries other translation units call --------------------------
+// byte offset of row r's chunk 0, slot s within a chunk-tiled f16 plane:
+// [r / 16][kc][r % 16][32]
+__device__ inline int64_t h2_frag_off(int r, int nkc, int slot) {
+  return (int64_t)(r >> 4) * nkc * 1024 + (r & 15) * 64 + slot * 16;
+}
+// search_h2.hip: the body of pps_search_h2_tiled / _excl / _rowmax (guards
+// included; fn names the entry in its messages; rowmax null = not wanted)
+int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q, const float* qsq,
+                    const float* qrs, const uint16_t* g2t, const float* gsq, const float* grs,
+                    int64_t G, int D, int metric, int k, int segments, int tile, void* workspace,
+                    int64_t ws_bytes, float* vals, int32_t* idx, const int32_t* q_group,
+                    const int32_t* g_group, float* rowmax, void* stream);
+// bytes that hold the workspace of a search of N rows against themselves, as a
+// bound that is non-decreasing in N (host arithmetic)
+int64_t search_h2_self_workspace_bound(int64_t N, int k, int segments);
+// pair_h2.hip: out[r][t] = distance of a-row r to b-row lists[r][t], t <
+// min(counts[r], cap) (lists / out rows cap apart; counts null = cap each);
+// the a operand is the first Q rows of planes holding Qrows rows
+int pair_dist_h2(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq, const float* qrs,
+                 const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
+                 int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
+                 hipStream_t st);
+// pair_h2.hip: the [M, N] block of the first M rows of an a operand holding
+// Arows rows against a whole b operand (pps_distmat_h2_tiled's launch and bits)
+int distmat_h2_head(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
+                    const float* ars, const uint16_t* b2t, const float* bsq, const float* brs,
+                    int64_t N, int D, int metric, float* out, int64_t ldo, hipStream_t st);
+
 // ---- evaluation counts (eval_counts.hip) ----------------------------------------
 int collect_matches(const float* dist, int64_t Q, int64_t ldd, const int32_t* qcam,
                     const int32_t* gcam, const int32_t* members, const int32_t* q_beg,
@@ -126,6 +155,25 @@ size_t rerank_workspace_bytes_for(const float* qg, int64_t ldqg, const float* qq
                                   int k2, int flags);
 // dynamic LDS of the Jaccard pass for a gallery of G
 size_t jaccard_lds_bytes(int64_t G);
+// Row-form re-ranking: OD(i, j) = rr_od(W[i][j], rowmax[i]) with
+// W[i][j] the general h2 kernel's value for a-row x_i, b-row x_j.  The OD
+// provider: W itself (the materialised twin), or the planes of x = [queries;
+// gallery] and of the gallery alone (the features path: no N x N buffer).
+constexpr int kJacMaxWindow = 38400;   // gallery rows of one Jaccard window (tm in LDS)
+struct RrRows {
+  const float* W;            // twin: [N][ldw]; null = the features path
+  int64_t ldw;
+  const uint16_t* x2t;       // features: x's planes, norms, scales (N rows)
+  const float* xsq; const float* xrs;
+  const uint16_t* g2t;       // the gallery rows' own planes (rows Q.. of x)
+  const float* gsq; const float* grs;
+  int D, metric, segments, tile;
+};
+int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
+                int64_t g_window, void* ws, size_t ws_bytes, float* out, hipStream_t st);
+// bytes of the workspace; features: the fused search's workspace included
+int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1, int k2,
+                                    int segments);
 
 // OD's arithmetic, float32 as NumPy does it (np.power(M, 2) then / colmax):
 // (m * m) / cm, both rounded (a product feeding a division cannot fuse), the

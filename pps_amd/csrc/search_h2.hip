@@ -60,6 +60,9 @@ struct SearchArgs {
   // q_group[r] >= 0 && g_group[c] == q_group[r] (global row / column)
   const int32_t* q_group;         // [Q]
   const int32_t* g_group;         // [G]
+  // ROWMAX kernels only: [Q], zeroed by the entry; receives the bits of
+  // max_c fl(d * d) over the real columns by atomicMax (squares are >= 0)
+  unsigned* rowmax;
 };
 
 // orders a wave's accesses to its candidate buffer in global memory (lane a's
@@ -87,7 +90,7 @@ __device__ inline unsigned long long uniform_u64(unsigned long long x) {
   return ((unsigned long long)hi << 32) | lo;
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool EXCL>
+template <int BM, int BN, int WM, int WN, int NS, bool EXCL, bool ROWMAX = false>
 __global__ void __launch_bounds__(64 * WM * WN)
 search_h2_kernel(GemmParams p, SearchArgs a) {
   using T = H2Tile<BM, BN, WM, WN, NS>;
@@ -177,12 +180,16 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
             thr = wave_cut<kSearchJ>(buf, n, k, kTkwSlack);
             wave_global_sync();
           }
+          float mx = 0.f;   // ROWMAX: max |d| of this lane's real columns
 #pragma unroll
           for (int j = 0; j < CS; ++j) {
             const int c = j * 64 + lane;
             // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
             const float dot = ok[j] ? t[row * LD + c] : 0.f;
             const float d = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
+            if constexpr (ROWMAX) {
+              if (ok[j]) mx = fmaxf(mx, fabsf(d));   // padded columns never count
+            }
             const unsigned long long packed =
                 ((unsigned long long)float_key(d) << 32) | (uint32_t)(n0 + c0h + c - cbase);
             bool take = ok[j] && packed <= thr;
@@ -196,6 +203,12 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
               buf[n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = packed;
             n += __popcll(bal);
+          }
+          if constexpr (ROWMAX) {
+            // fl(d * d) is monotone in |d|: one square of the pass's maximum
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+            if (lane == 0) atomicMax(a.rowmax + gr, __float_as_uint(mx * mx));
           }
           if (lane == 0) {
             s_thr[row] = thr;
@@ -277,13 +290,33 @@ static SearchLayout search_layout(int64_t Q, int64_t G, int k, int segments) {
   return L;
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool EXCL>
+template <int BM, int BN, int WM, int WN, int NS, bool EXCL, bool ROWMAX>
 static int launch_search(const GemmParams& p, SearchArgs a, hipStream_t st) {
   const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
-  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS, EXCL>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS, EXCL, ROWMAX>), dim3((unsigned)grid),
                      dim3(64 * WM * WN), 0, st, p, a);
   PPS_CHECK_LAUNCH("search_h2_kernel");
   return PPS_OK;
+}
+
+// the two tile shapes of one filter variant
+template <bool EXCL, bool ROWMAX>
+static int launch_search_tile(int tile, const GemmParams& p, const SearchArgs& a, hipStream_t st) {
+  return tile == 2 ? launch_search<192, 192, 2, 4, 3, EXCL, ROWMAX>(p, a, st)
+                   : launch_search<256, 256, 2, 4, 2, EXCL, ROWMAX>(p, a, st);
+}
+
+// An upper bound of search_layout(N, N, k, segments).total (a self-search: the
+// queries grow with the gallery, and the auto segment count then falls in
+// steps) that is non-decreasing in N.  S <= the gallery's tiles and <= the
+// request; auto: S <= 2 kSearchSlots / panels <= 512 BM / N, so S * N <= 2^17.
+int64_t search_h2_self_workspace_bound(int64_t N, int k, int segments) {
+  const int64_t tiles = std::max<int64_t>(cdiv(N, 192), 1);   // the finer tile shape's count
+  const int64_t slots = std::min<int64_t>(kSearchSlots, tiles * tiles);
+  const int64_t by_req = segments > 0 ? N * std::min<int64_t>(segments, kMergeMaxLists)
+                                      : std::max<int64_t>(N, 2 * kSearchSlots * kSearchMaxBM);
+  const int64_t entries = k * std::min<int64_t>(by_req, N * tiles);
+  return align256(slots * kSearchMaxBM * search_cap(k) * 8) + 2 * align256(entries * 4);
 }
 
 }  // namespace pps
@@ -300,13 +333,14 @@ int64_t pps_search_h2_workspace_bytes(int64_t Q, int64_t G, int k, int segments)
   return search_layout(Q, G, k, segments).total;
 }
 
-// pps_search_h2_tiled (excl false) and pps_search_h2_tiled_excl (excl true)
-static int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q,
-                           const float* qsq, const float* qrs, const uint16_t* g2t, const float* gsq,
-                           const float* grs, int64_t G, int D, int metric, int k, int segments,
-                           int tile, void* workspace, int64_t ws_bytes, float* vals,
-                           int32_t* idx, const int32_t* q_group, const int32_t* g_group,
-                           void* stream) {
+// pps_search_h2_tiled (excl false), pps_search_h2_tiled_excl (excl true) and
+// pps_search_h2_tiled_rowmax (rowmax given, no exclusion)
+int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q,
+                         const float* qsq, const float* qrs, const uint16_t* g2t, const float* gsq,
+                         const float* grs, int64_t G, int D, int metric, int k, int segments,
+                         int tile, void* workspace, int64_t ws_bytes, float* vals,
+                         int32_t* idx, const int32_t* q_group, const int32_t* g_group,
+                         float* rowmax, void* stream) {
   PPS_ENFORCE(vals && idx, "null pointer");
   PPS_ENFORCE(!excl || (q_group && g_group), "null group pointer");
   PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
@@ -322,6 +356,7 @@ static int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64
   if (Q == 0) return PPS_OK;
   hipStream_t st = as_stream(stream);
   if (G == 0) {  // nothing to rank: pad entries only
+    if (rowmax) (void)hipMemsetAsync(rowmax, 0, sizeof(float) * Q, st);
     const int64_t n = Q * k;
     hipLaunchKernelGGL(search_fill_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                        vals, idx, n);
@@ -355,6 +390,8 @@ static int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64
   a.pidx = reinterpret_cast<int32_t*>(ws + L.cand_bytes + (L.total - L.cand_bytes) / 2);
   a.q_group = q_group;
   a.g_group = g_group;
+  a.rowmax = reinterpret_cast<unsigned*>(rowmax);
+  if (rowmax) (void)hipMemsetAsync(rowmax, 0, sizeof(float) * Q, st);   // the atomicMax's zero
 
   GemmParams p{};
   p.splitk = 1;
@@ -368,10 +405,9 @@ static int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64
   p.rs_a = qrs; p.rs_b = grs;
   p.metric = metric;
 
-  const int rc = excl ? (tile == 2 ? launch_search<192, 192, 2, 4, 3, true>(p, a, st)
-                                   : launch_search<256, 256, 2, 4, 2, true>(p, a, st))
-                      : (tile == 2 ? launch_search<192, 192, 2, 4, 3, false>(p, a, st)
-                                   : launch_search<256, 256, 2, 4, 2, false>(p, a, st));
+  const int rc = excl ? launch_search_tile<true, false>(tile, p, a, st)
+                      : (rowmax ? launch_search_tile<false, true>(tile, p, a, st)
+                                : launch_search_tile<false, false>(tile, p, a, st));
   if (rc != PPS_OK) return rc;
   MergeOffsets offs{};
   for (int s = 0; s < a.S; ++s) offs.off[s] = (int64_t)s * a.tps * BN;
@@ -384,7 +420,18 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
                         int64_t ws_bytes, float* vals, int32_t* idx, void* stream) {
   return search_h2_tiled("pps_search_h2_tiled", false, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
                          metric, k, segments, tile, workspace, ws_bytes, vals, idx, nullptr,
-                         nullptr, stream);
+                         nullptr, nullptr, stream);
+}
+
+int pps_search_h2_tiled_rowmax(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                               const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
+                               int D, int metric, int k, int segments, int tile, void* workspace,
+                               int64_t ws_bytes, float* vals, int32_t* idx, float* rowmax,
+                               void* stream) {
+  PPS_ENFORCE(rowmax, "null pointer");
+  return search_h2_tiled("pps_search_h2_tiled_rowmax", false, q2t, Q, qsq, qrs, g2t, gsq, grs, G,
+                         D, metric, k, segments, tile, workspace, ws_bytes, vals, idx, nullptr,
+                         nullptr, rowmax, stream);
 }
 
 int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
@@ -394,5 +441,5 @@ int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, c
                              const int32_t* q_group, const int32_t* g_group, void* stream) {
   return search_h2_tiled("pps_search_h2_tiled_excl", true, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
                          metric, k, segments, tile, workspace, ws_bytes, vals, idx, q_group,
-                         g_group, stream);
+                         g_group, nullptr, stream);
 }

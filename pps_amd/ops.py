@@ -1236,6 +1236,140 @@ def self_distance_blocks(x, Q, metric='euclidean'):
     return M, M[:Q, Q:], M[:Q, :Q], M[Q:, Q:]
 
 
+def search_rowmax(q, index, k, metric='euclidean', segments=0, tile=0, workspace=None):
+    """search against one h2 GalleryIndex that also returns every query's
+    largest squared distance: -> (vals [Q, k], idx [Q, k], rowmax [Q]) with
+    vals / idx exactly search's and rowmax the bits of (W * W).amax(1), W =
+    compute_dist(q, index, math='h2', symmetric=False) -- over the G real
+    columns (pps_search_h2_tiled_rowmax; the matrix is never written).  There
+    is no fallback: q must be contiguous with D % 32 == 0 and k <=
+    search_max_k()."""
+    if not isinstance(index, GalleryIndex) or index.h2 is None:
+        raise RuntimeError('search_rowmax: the gallery must be a GalleryIndex holding an h2 split')
+    if q.dim() != 2 or q.shape[1] != index.shape[1]:
+        raise RuntimeError('search_rowmax expects [Q, D] queries and a [G, D] gallery')
+    Q, D = q.shape
+    G = index.shape[0]
+    k = int(k)
+    if D % 32 != 0 or not q.is_contiguous() or not 1 <= k <= search_max_k():
+        raise RuntimeError('search_rowmax: needs contiguous queries, D %% 32 == 0 and '
+                           '1 <= k <= %d' % search_max_k())
+    q2, qrs, qsq = split_h2_tiled(q)
+    g2, grs, gsq = index.h2
+    need = search_workspace_bytes(Q, G, k, segments)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=q.device)
+    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
+          not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError('search_rowmax: workspace must be a contiguous device tensor of at '
+                           'least %d bytes (search_workspace_bytes)' % need)
+    vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+    rowmax = torch.empty((Q,), dtype=torch.float32, device=q.device)
+    call('pps_search_h2_tiled_rowmax', _dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
+         _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
+         D, METRICS[metric], k, int(segments), int(tile), workspace.data_ptr(),
+         workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr(),
+         rowmax.data_ptr(), _stream())
+    return vals, idx, rowmax
+
+
+def pair_dist(q, index, lists, counts=None, metric='euclidean'):
+    """Distances of listed pairs without the matrix (pps_pair_dist_h2):
+    out[r, t] = the distance of query r to gallery row lists[r, t] for t <
+    min(counts[r], cap), with the bits compute_dist(q, index, math='h2',
+    symmetric=False) holds at that cell; cells past a row's count are 0.
+    lists [Q, cap] int32, counts [Q] int32 or None (every entry).  q: the
+    [Q, D] queries, or their split_h2_tiled triple."""
+    q_split = q if isinstance(q, tuple) else split_h2_tiled(q)
+    args = _h2_operands('pair_dist', q_split, index)
+    Q = args[1]
+    if lists.dim() != 2 or lists.shape[0] != Q or lists.shape[1] < 1:
+        raise RuntimeError('pair_dist: lists must be [%d, cap >= 1]' % Q)
+    cap = lists.shape[1]
+    if counts is not None and tuple(counts.shape) != (Q,):
+        raise RuntimeError('pair_dist: counts must be [%d]' % Q)
+    out = torch.zeros((Q, cap), dtype=torch.float32, device=lists.device)
+    call('pps_pair_dist_h2', *(args + (
+        METRICS[metric], _dev(lists, 'lists', torch.int32),
+        0 if counts is None else _dev(counts, 'counts', torch.int32), cap, out.data_ptr(),
+        _stream())))
+    return out
+
+
+def rerank_rows_workspace_bytes(Q, G, k1=20, k2=6, features=False, segments=0):
+    """Bytes of workspace of re_ranking_rows (features=False) or
+    re_ranking_from_features (host arithmetic, non-decreasing in G): per-row
+    structures only, about 27 KB a row at (20, 6), plus the fused search's
+    workspace on the features path."""
+    L = _lib.lib()
+    n = int(L.pps_rerank_features_workspace_bytes(int(Q), int(G), int(k1), int(k2), int(segments))
+            if features else L.pps_rerank_rows_workspace_bytes(int(Q), int(G), int(k1), int(k2)))
+    if n < 0:
+        raise RuntimeError('rerank_rows_workspace_bytes: bad arguments Q=%r G=%r k1=%r k2=%r '
+                           'segments=%r' % (Q, G, k1, k2, segments))
+    return n
+
+
+def re_ranking_rows(W, Q, k1=20, k2=6, lambda_value=0.3, g_window=0):
+    """Row-form k-reciprocal re-ranking from a materialised [N, N] matrix W of
+    x = [queries; gallery] (the first Q rows the queries) -> [Q, G]: the twin
+    of re_ranking_from_features (pps_re_ranking_rows).  Row i's
+    neighbours are its stable (W[i, j], j) top-(k1 + 1), OD(i, j) =
+    W[i, j]^2 / max_j W[i, j]^2; W need not be symmetric (the general h2
+    kernel's, compute_dist(x, GalleryIndex(x), symmetric=False), is not).
+    g_window: gallery rows per Jaccard workgroup (0 = auto; same bits)."""
+    _dev_rows(W, 'W')
+    N = W.shape[0]
+    if W.shape[1] != N or not 0 < Q < N:
+        raise RuntimeError('re_ranking_rows: W must be [N, N] with 0 < Q < N, got %s, Q=%r'
+                           % (tuple(W.shape), Q))
+    G = N - Q
+    nbytes = rerank_rows_workspace_bytes(Q, G, k1, k2)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=W.device)
+    out = torch.empty((Q, G), dtype=torch.float32, device=W.device)
+    call('pps_re_ranking_rows', W.data_ptr(), _ld(W), Q, G, int(k1), int(k2),
+         float(lambda_value), int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())
+    return out
+
+
+def re_ranking_from_features(x, Q, k1=20, k2=6, lambda_value=0.3, metric='euclidean', segments=0,
+                             tile=0, g_window=0):
+    """k-reciprocal re-ranking straight from the features x = [queries;
+    gallery] ([N, D], the first Q rows the queries) -> [Q, G], without any
+    [N, N] buffer and for any gallery size (pps_re_ranking_features; DESIGN
+    6.1.4): ranks and row maxima from the fused search of x against itself,
+    the weights' distances from the pair kernel, the q x g block computed into
+    the result and blended in place.  Bit for bit re_ranking_rows on W =
+    compute_dist(x, GalleryIndex(x), symmetric=False).  Holds the planes of x,
+    a second copy of the gallery's planes and per-row structures (about 27 KB
+    a row at k1 = 20, k2 = 6).  One h2 index only (x's planes under 2 GiB).
+    Raises -- it never builds an [N, N] matrix silently -- when x is strided,
+    D % 32 != 0 or the distance arithmetic is not h2: use re_ranking_rows on a
+    matrix of your own then."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise RuntimeError('re_ranking_from_features: x must be a [N, D] tensor')
+    N, D = x.shape
+    if not x.is_contiguous() or D % 32 != 0 or dist_math() != 'h2':
+        raise RuntimeError('re_ranking_from_features: needs contiguous features, D %% 32 == 0 '
+                           'and h2 distance arithmetic (got stride %s, D=%d, math %r); '
+                           're_ranking_rows takes a materialised matrix instead'
+                           % (x.stride(), D, dist_math()))
+    if not 0 < Q < N:
+        raise RuntimeError('re_ranking_from_features: need 0 < Q < N, got Q=%r N=%d' % (Q, N))
+    G = N - Q
+    x2, xrs, xsq = split_h2_tiled(x)
+    g2, grs, gsq = split_h2_tiled(x[Q:])
+    nbytes = rerank_rows_workspace_bytes(Q, G, k1, k2, features=True, segments=segments)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((Q, G), dtype=torch.float32, device=x.device)
+    call('pps_re_ranking_features', _dev(x2, 'x2t', torch.int16), _dev(xsq, 'xsq'),
+         _dev(xrs, 'xrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), Q, G,
+         D, METRICS[metric], int(k1), int(k2), float(lambda_value), int(segments), int(tile),
+         int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())
+    return out
+
+
 def max_positives(qid, qcam, gid, gcam):
     """Host-side bound on true matches per query (metadata only, exact)."""
     qid = np.asarray(qid, np.int64)

@@ -399,7 +399,13 @@ def evaluate(json_dataset, all_feats, output_dir, verbose=True):
     return evaluate_arrays(all_feats, ids, cams, marks, verbose=verbose)
 
 
-def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None):
+def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None,
+                    rerank_from_features=False):
+    """rerank_from_features: with cfg.REID.RERANK, the re-ranked single-query
+    and multi-query scores come from ops.re_ranking_from_features (row-form
+    re-ranking from the features: no [N, N] matrix, any gallery size) instead
+    of the self-distance matrix + ops.re_ranking.  One gallery index only; the
+    sharded evaluator keeps the matrix path."""
     metric = metric or cfg.REID.get('DISTANCE', 'euclidean')
     feat = _to_dev(all_feats)
     ids, cams, marks = np.asarray(ids), np.asarray(cams), np.asarray(marks)
@@ -418,7 +424,7 @@ def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None):
     # re-ranking on the h2 / x3 paths: ONE mirrored self-distance of [queries;
     # gallery] gives q_g, q_q and g_g as blocks of one exactly symmetric
     # matrix (re-ranking then reads q_g^T in place, PPS_RERANK_WHOLE)
-    whole = bool(cfg.REID.RERANK) and tiled
+    whole = bool(cfg.REID.RERANK) and tiled and not rerank_from_features
     if whole:
         x = feat.index_select(0, torch.cat([qi, gi])).contiguous()
         qf, gf = x[:len(qi)], x[len(qi):]
@@ -464,7 +470,9 @@ def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None):
         # :161-207 -- re-ranked scores overwrite the plain ones
         with measure_time('Re-ranking distance...', verbose):
             # 16-byte rows: re-ranking reads the blocks in place (no N x N copy)
-            if whole:
+            if rerank_from_features:
+                rr = ops.re_ranking_from_features(torch.cat([qf, gf]), len(qi), metric=metric)
+            elif whole:
                 rr = ops.re_ranking(q_g, q_q, g_g, symmetric=True, whole=True)
             else:
                 q_q = ops.compute_dist(qf, qf, metric=metric, pad_rows=True)
@@ -478,10 +486,14 @@ def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None):
             print_scores(mAP, cmc_scores)
         if mq_inds.any():
             with measure_time('Multi Query, Re-ranking distance...', verbose):
-                mq_mq = ops.compute_dist(pooled, pooled, metric=metric, pad_rows=True)
-                # g_g a block of the whole matrix: exactly symmetric, untagged
-                sym = True if whole and getattr(mq_mq, '_pps_symmetric', False) else None
-                rr_mq = ops.re_ranking(mq_g, mq_mq, g_g, symmetric=sym)
+                if rerank_from_features:
+                    rr_mq = ops.re_ranking_from_features(torch.cat([pooled, gf]), len(pooled),
+                                                         metric=metric)
+                else:
+                    mq_mq = ops.compute_dist(pooled, pooled, metric=metric, pad_rows=True)
+                    # g_g a block of the whole matrix: exactly symmetric, untagged
+                    sym = True if whole and getattr(mq_mq, '_pps_symmetric', False) else None
+                    rr_mq = ops.re_ranking(mq_g, mq_mq, g_g, symmetric=sym)
             with measure_time('Multi Query, Computing scores for re-ranked distance...',
                               verbose):
                 mq_mAP, mq_cmc = compute_score(rr_mq, keys[:, 0], ids[g_inds], keys[:, 1],
@@ -497,4 +509,17 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3):
     as_numpy = not isinstance(q_g_dist, torch.Tensor)
     out = ops.re_ranking(_to_dev(q_g_dist), _to_dev(q_q_dist), _to_dev(g_g_dist), k1, k2,
                          lambda_value)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def re_ranking_from_features(query_feats, gallery_feats, k1=20, k2=6, lambda_value=0.3,
+                             metric='euclidean', segments=0, tile=0, g_window=0):
+    """Row-form re-ranking straight from the features (ops.re_ranking_from_features:
+    no [N, N] matrix, any gallery size) -> [Q, G]; NumPy in -> NumPy out, CUDA
+    tensors in -> tensor out."""
+    as_numpy = not isinstance(query_feats, torch.Tensor)
+    q, g = _to_dev(query_feats), _to_dev(gallery_feats)
+    out = ops.re_ranking_from_features(torch.cat([q, g]), q.shape[0], k1, k2, lambda_value,
+                                       metric=metric, segments=segments, tile=tile,
+                                       g_window=g_window)
     return out.cpu().numpy() if as_numpy else out
