@@ -505,20 +505,21 @@ int pps_re_ranking(const float* q_g, const float* q_q, const float* g_g, int64_t
 // runs before anything is launched
 static int rerank_rows_guards(const char* fn, int64_t Q, int64_t G, int k1, int k2,
                               int64_t g_window) {
-  PPS_ENFORCE(Q > 0 && G > 0, "bad shape");
-  PPS_ENFORCE(Q + G < (1ll << 31), "N = Q + G must fit int32");
-  PPS_ENFORCE(k1 >= 1 && k1 + 1 <= 64 && k1 + 1 <= kTkwMaxK,
-              "k1 + 1 must be <= 64 and <= pps_search_max_k()");
-  PPS_ENFORCE(k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
+  PPS_ENFORCE_AS(fn, Q > 0 && G > 0, "bad shape");
+  PPS_ENFORCE_AS(fn, Q + G < (1ll << 31), "N = Q + G must fit int32");
+  PPS_ENFORCE_AS(fn, k1 >= 1 && k1 + 1 <= 64 && k1 + 1 <= kTkwMaxK,
+                 "k1 + 1 must be <= 64 and <= pps_search_max_k()");
+  PPS_ENFORCE_AS(fn, k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
   const int K1 = k1 + 1, Kh = (int)lrint(k1 / 2.0) + 1;
-  PPS_ENFORCE(K1 + K1 * Kh <= 1024, "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
+  PPS_ENFORCE_AS(fn, K1 + K1 * Kh <= 1024,
+                 "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
   const int vcap = K1 + K1 * Kh <= 256 ? 256 : (K1 + K1 * Kh <= 512 ? 512 : 1024);
-  PPS_ENFORCE(k2 * vcap <= 4096, "k2 * V row capacity must be <= 4096");
-  PPS_ENFORCE((Q + G) >= K1, "need Q + G >= k1 + 1");
-  PPS_ENFORCE(g_window >= 0 && g_window <= kJacMaxWindow,
-              "g_window must be in [0, " + std::to_string(kJacMaxWindow) + "] (0 = auto)");
-  PPS_ENFORCE(g_window == 0 || (G + g_window - 1) / g_window <= 65535,
-              "more than 65535 gallery windows");
+  PPS_ENFORCE_AS(fn, k2 * vcap <= 4096, "k2 * V row capacity must be <= 4096");
+  PPS_ENFORCE_AS(fn, (Q + G) >= K1, "need Q + G >= k1 + 1");
+  PPS_ENFORCE_AS(fn, g_window >= 0 && g_window <= kJacMaxWindow,
+                 "g_window must be in [0, " + std::to_string(kJacMaxWindow) + "] (0 = auto)");
+  PPS_ENFORCE_AS(fn, g_window == 0 || (G + g_window - 1) / g_window <= 65535,
+                 "more than 65535 gallery windows");
   if ((Q + G) * (int64_t)(k2 * vcap) >= (1ll << 31)) {
     set_error(std::string(fn) + ": N * qcap = " + std::to_string(Q + G) + " * " +
               std::to_string(k2 * vcap) + " entries of the inverted index do not fit int32");
@@ -536,8 +537,7 @@ int pps_re_ranking_rows(const float* W, int64_t ldw, int64_t Q, int64_t G, int k
                         double lambda_value, int64_t g_window, void* workspace, int64_t ws_bytes,
                         float* out, void* stream) {
   PPS_ENFORCE(W && workspace && out, "null pointer");
-  const int rc = rerank_rows_guards("pps_re_ranking_rows", Q, G, k1, k2, g_window);
-  if (rc != PPS_OK) return rc;
+  PPS_TRY(rerank_rows_guards(__func__, Q, G, k1, k2, g_window));
   PPS_ENFORCE(ldw >= Q + G, "ldw smaller than the rows");
   PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   RrRows src{};
@@ -559,16 +559,11 @@ int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* 
                             int64_t G, int D, int metric, int k1, int k2, double lambda_value,
                             int segments, int tile, int64_t g_window, void* workspace,
                             int64_t ws_bytes, float* out, void* stream) {
-  PPS_ENFORCE(x2t && xsq && xrs && g2t && gsq && grs && workspace && out, "null pointer");
-  PPS_ENFORCE(D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
-  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
-  const int rc = rerank_rows_guards("pps_re_ranking_features", Q, G, k1, k2, g_window);
-  if (rc != PPS_OK) return rc;
-  PPS_ENFORCE(2 * ((Q + G + 15) / 16 * 16) * D * 2 < kMaxBufBytes, "planes over 2 GiB");
-  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
-  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
-              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
-  PPS_ENFORCE(aligned16(x2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  PPS_ENFORCE(workspace && out, "null pointer");
+  PPS_TRY(rerank_rows_guards(__func__, Q, G, k1, k2, g_window));   // Q, G > 0, N in int32
+  // the operands: x = [queries; gallery] (N rows) and the gallery rows' own planes
+  PPS_TRY(h2_operands_guard(__func__, x2t, Q + G, xsq, xrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(fused_plan_guard(__func__, segments, tile));
   PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   RrRows src{};
   src.x2t = x2t; src.xsq = xsq; src.xrs = xrs;

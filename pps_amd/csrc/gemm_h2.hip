@@ -35,6 +35,7 @@
 // when the tile's f32 image exceeds it) and writes whole row segments.
 // The K loop itself lives in gemm_h2_common.hpp (shared with search_h2.hip).
 #include "gemm_h2_common.hpp"
+#include "retrieval.hpp"
 
 namespace pps {
 
@@ -358,38 +359,17 @@ int pps_split_f16x2_sqnorm_tiled(const float* x, int64_t rows, int D, int64_t ld
   return split_h2_sqnorm_tiled(x, rows, D, ld, out2t, rscale, sqnorm, as_stream(stream));
 }
 
-static GemmParams h2_params(const uint16_t* a2t, int64_t M, const float* asq, const float* ars,
-                            const uint16_t* b2t, int64_t N, const float* bsq, const float* brs,
-                            int D, int metric, float* out, int64_t ldo, int sym) {
-  const int64_t Mp = (M + 15) / 16 * 16, Np = (N + 15) / 16 * 16;
-  GemmParams p{};
-  p.splitk = 1;
-  p.tiled = 3;
-  p.a3 = a2t; p.a_plane = Mp * D; p.a_bytes = (uint32_t)(2 * Mp * D * 2);
-  p.M = (int)M;
-  p.b3 = b2t; p.b_plane = Np * D; p.b_bytes = (uint32_t)(2 * Np * D * 2);
-  p.Ncol = (int)N;
-  p.Kloop = D;
-  p.norm_a = asq; p.norm_b = bsq;
-  p.rs_a = ars; p.rs_b = brs;
-  p.out = out; p.ldo = ldo; p.metric = metric; p.sym = sym;
-  return p;
-}
-
 int pps_distmat_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
                          const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
                          int D, int metric, float* out, int64_t ldo, int tile, void* stream) {
+  // empty operands included: the pointers and their alignment are checked for every shape
   PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs && out, "null pointer");
-  PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
-  PPS_ENFORCE(ldo >= G, "ldo < G");
   PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
-  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
+  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_ENFORCE(ldo >= G, "ldo < G");
   PPS_ENFORCE(tile >= 0 && tile < kH2NumTiles, "h2 tile must be 0.." + std::to_string(kH2NumTiles - 1));
-  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
-  PPS_ENFORCE(2 * Qp * D * 2 < kMaxBufBytes && 2 * Gp * D * 2 < kMaxBufBytes,
-              "planes over 2 GiB");
   if (Q == 0 || G == 0) return PPS_OK;
-  const GemmParams p = h2_params(q2t, Q, qsq, qrs, g2t, G, gsq, grs, D, metric, out, ldo, 0);
+  const GemmParams p = h2_params(q2t, Q, Q, qsq, qrs, g2t, G, gsq, grs, D, metric, out, ldo);
   return launch_gemm_h2(p, as_stream(stream), tile);
 }
 
@@ -402,10 +382,9 @@ int pps_distmat_h2_self_tiled(const uint16_t* x2t, int64_t N, const float* xsq, 
   PPS_ENFORCE(aligned16(x2t), "x2t must be 16-byte aligned");
   PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
   PPS_ENFORCE(tile >= 0 && tile < kH2NumTiles, "h2 tile must be 0.." + std::to_string(kH2NumTiles - 1));
-  const int64_t Np = (N + 15) / 16 * 16;
-  PPS_ENFORCE(2 * Np * D * 2 < kMaxBufBytes, "planes over 2 GiB");
+  PPS_ENFORCE(h2_planes_bytes(N, D) < kMaxBufBytes, "planes over 2 GiB");
   PPS_ENFORCE(N * ldo < (1ll << 31), "output larger than 2^31 elements");
   if (N == 0) return PPS_OK;
-  const GemmParams p = h2_params(x2t, N, xsq, xrs, x2t, N, xsq, xrs, D, metric, out, ldo, 1);
+  const GemmParams p = h2_params(x2t, N, N, xsq, xrs, x2t, N, xsq, xrs, D, metric, out, ldo, 1);
   return launch_gemm_h2(p, as_stream(stream), tile);
 }

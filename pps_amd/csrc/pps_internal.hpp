@@ -12,13 +12,22 @@ namespace pps {
 // Thread-local ENFORCE-style error message (pps_last_error()).
 void set_error(const std::string& msg);
 
-#define PPS_ENFORCE(cond, msg)                                              \
-  do {                                                                      \
-    if (!(cond)) {                                                          \
-      ::pps::set_error(std::string("[enforce fail at ") + __func__ + "] " + \
-                       #cond + ". " + (msg));                               \
-      return PPS_ERR_INVALID_ARG;                                           \
-    }                                                                       \
+#define PPS_ENFORCE_TEXT(fn, cond, text, msg)                                         \
+  do {                                                                                \
+    if (!(cond)) {                                                                    \
+      ::pps::set_error(std::string("[enforce fail at ") + (fn) + "] " + text + ". " + \
+                       (msg));                                                        \
+      return PPS_ERR_INVALID_ARG;                                                     \
+    }                                                                                 \
+  } while (0)
+#define PPS_ENFORCE(cond, msg) PPS_ENFORCE_TEXT(__func__, cond, #cond, msg)
+// in a guard several entry points share: fn is the entry's name
+#define PPS_ENFORCE_AS(fn, cond, msg) PPS_ENFORCE_TEXT(fn, cond, #cond, msg)
+// pass a helper's failure on to the caller
+#define PPS_TRY(call)                \
+  do {                               \
+    const int rc_ = (call);          \
+    if (rc_ != PPS_OK) return rc_;   \
   } while (0)
 
 // PPS_DEBUG_SYNC=1 (debug only; breaks hipGraph capture): synchronize after

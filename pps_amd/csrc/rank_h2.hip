@@ -1,27 +1,17 @@
-// Matrix-free rank counts ("fused mAP"): the two kernels of the count-based
-// evaluation that read the [Q, G] distance matrix (eval_counts.hip:
-// collect_matches, rank_count_stream), each with a twin that computes the
-// f16x2 distances on the fly from the operands' chunk-tiled planes.  Every
-// distance has the bits pps_distmat_h2_tiled would have written -- a cell's
-// accumulator depends only on its own query row, its own gallery row and the
-// order of the MFMA terms (chunks ascending, mfma_h2t's three terms), and the
-// finish is the same expression, dist_value(p, (acc * rs_a) * rs_b, qn, gn) --
-// so the lists and counts equal the materialised path's exactly and
-// rank_prepare / ap_finalize run unchanged between and after the two.
+// Matrix-free rank counts ("fused mAP" and the fractional / separate-camera
+// CMC): rank_count_stream's and cmc_count_kernel's twin (eval_counts.hip) that
+// computes the f16x2 distances on the fly from the operands' chunk-tiled planes
+// instead of reading the [Q, G] matrix.  Every distance has the bits
+// pps_distmat_h2_tiled would have written (h2_fused_common.hpp), so the counts
+// equal the materialised path's exactly and rank_prepare / ap_finalize /
+// cmc_finalize run unchanged around it.  This file holds the count kernel, its
+// two junk follow-ups and the two count entry points; the lists the counts are
+// taken against come from pps_collect_matches_h2 (pair_h2.hip).
 //
-// a) collect_matches_h2: one wave per query.  Its members (the MatchIndex
-//    CSR) are taken 64 at a time as four blocks of 16 MFMA columns; per K
-//    chunk each lane loads its 16-byte fragments straight from the tiled
-//    planes in global memory (the member's row and the query's row, slot
-//    lane >> 4, both planes; no LDS staging).  All 16 query rows of the MFMA
-//    are the one query, so every lane group holds a copy of the block's 16
-//    dot products; one cross-lane move hands lane i member m0 + i's, and the
-//    positive / junk split and the compaction are collect_matches'.
-//
-// b) rank_count_h2: search_h2_kernel's skeleton (work item = query panel x
-//    gallery segment, workgroups striding over the items, h2_kloop per tile,
-//    accumulators parked in LDS, each wave finishing BM / 8 rows) with a
-//    counting epilogue in place of the candidate filter.  A row's first and
+// rank_count_h2_kernel: the fused frame of h2_fused_common.hpp (work item =
+//    query panel x gallery segment, workgroups striding over the items,
+//    h2_kloop per tile, accumulators parked in LDS, each wave finishing BM / 8
+//    rows) with a counting epilogue.  A row's first and
 //    last positive distance (df, dmax), the first positive's index and its
 //    list length sit in 16 B of LDS row state.  A pass none of whose columns
 //    has d <= dmax is left after one ballot per 64 columns (the common case:
@@ -44,121 +34,20 @@
 //    distances) are taken back out by a small follow-up kernel on the same
 //    stream, as rank_count_stream's chunk 0 does.
 //
-// c) cmc_count_h2 (the fractional and the separate-camera CMC): b)'s kernel
-//    with cmc_count_kernel's key bins in place of the distance bins (its KEY
-//    parameter, described at kBinDist below) -- pps_cmc_counts on the h2
-//    matrix, exactly; pps_cmc_finalize runs unchanged after it.
+// Its KEY parameter (kBinDist below) chooses the bins: the distance bins of
+//    mAP, or cmc_count_kernel's key bins -- pps_cmc_counts on the h2 matrix,
+//    exactly.
 //
 // No workgroup waits on another; nothing is launched cooperatively.
 #include <algorithm>
 
-#include "gemm_h2_common.hpp"
-#include "retrieval.hpp"
+#include "h2_fused_common.hpp"
 #include "topk_wave_common.hpp"
 
 namespace pps {
 
-// ---- a) matches' distances ----------------------------------------------------
-constexpr int kPairWaves = 4;
-
-struct PairArgs {
-  const unsigned char* q2t;   // planes as bytes
-  const unsigned char* g2t;
-  int64_t q_plane, g_plane;   // bytes between an operand's two planes
-  const float* qsq; const float* qrs;
-  const float* gsq; const float* grs;
-  int64_t Q;
-  int nkc, metric;
-  const int32_t* qcam; const int32_t* gcam;
-  const int32_t* members; const int32_t* q_beg; const int32_t* q_end;
-  int64_t g_offset;
-  int Pmax, Jmax;
-  float* pos_d; int32_t* pos_idx; int32_t* pos_cnt;
-  float* junk_d; int32_t* junk_idx; int32_t* junk_cnt;
-};
-
-// h2_frag_off (a row's fragment in a chunk-tiled plane): retrieval.hpp
-
-__global__ void __launch_bounds__(64 * kPairWaves)
-collect_matches_h2_kernel(PairArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t q = (int64_t)blockIdx.x * kPairWaves + (threadIdx.x >> 6);
-  if (q >= a.Q) return;   // wave-uniform: every MFMA below runs with all lanes
-  const int beg = __builtin_amdgcn_readfirstlane(a.q_beg[q]);
-  const int end = __builtin_amdgcn_readfirstlane(a.q_end[q]);
-  const int qc = a.qcam[q];
-  const int r16 = lane & 15, slot = lane >> 4;
-  const unsigned char* qa = a.q2t + h2_frag_off((int)q, a.nkc, slot);
-  const float qn = a.qsq[q], ra = a.qrs[q];
-  GemmParams p{};
-  p.metric = a.metric;
-  // lane i's member sits in block i >> 4, column i & 15: register i & 3 of the
-  // lanes 16 ((i & 15) >> 2) + r, any r.  Every lane picks register
-  // (r >> 2, r & 3) of its own; lane i then reads lane
-  // 16 ((i & 15) >> 2) + 4 (i >> 4) + (i & 3).
-  const int src = 16 * ((lane & 15) >> 2) + 4 * (lane >> 4) + (lane & 3);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int np = 0, nj = 0;
-  for (int m0 = beg; m0 < end; m0 += 64) {
-    const int nb = min(4, (end - m0 + 15) >> 4);   // blocks with a member (wave-uniform)
-    const unsigned char* ga[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      // columns past the list repeat its last member (their cells are not read)
-      const int mi = min(m0 + 16 * b + r16, end - 1);
-      ga[b] = a.g2t + h2_frag_off(a.members[mi], a.nkc, slot);
-    }
-    f32x4 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int kc = 0; kc < a.nkc; ++kc) {
-      const int64_t ko = (int64_t)kc * 1024;
-      const f16x8 q0 = *reinterpret_cast<const f16x8*>(qa + ko);
-      const f16x8 q1 = *reinterpret_cast<const f16x8*>(qa + a.q_plane + ko);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        if (b < nb) {
-          const f16x8 g0 = *reinterpret_cast<const f16x8*>(ga[b] + ko);
-          const f16x8 g1 = *reinterpret_cast<const f16x8*>(ga[b] + a.g_plane + ko);
-          acc[b] = mfma_h2t(q0, q1, g0, g1, acc[b]);
-        }
-      }
-    }
-    const int rb4 = r16 >> 2, re = lane & 3;
-    const f32x4 t = rb4 == 0 ? acc[0] : rb4 == 1 ? acc[1] : rb4 == 2 ? acc[2] : acc[3];
-    const float mine = re == 0 ? t[0] : re == 1 ? t[1] : re == 2 ? t[2] : t[3];
-    const float dot = __shfl(mine, src);
-
-    const int m = m0 + lane;
-    const bool in = m < end;
-    const int idx = in ? a.members[m] : 0;
-    const bool pos = in && a.gcam[idx] != qc;
-    const bool junk = in && !pos;
-    // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
-    const float d = in ? dist_value(p, (dot * ra) * a.grs[idx], qn, a.gsq[idx]) : 0.f;
-    const unsigned long long bp = __ballot(pos), bj = __ballot(junk);
-    const int sp = np + __popcll(bp & below), sj = nj + __popcll(bj & below);
-    if (pos && sp < a.Pmax) {
-      a.pos_d[q * a.Pmax + sp] = d;
-      a.pos_idx[q * a.Pmax + sp] = (int32_t)(a.g_offset + idx);
-    }
-    if (junk && sj < a.Jmax) {
-      a.junk_d[q * a.Jmax + sj] = d;
-      a.junk_idx[q * a.Jmax + sj] = (int32_t)(a.g_offset + idx);
-    }
-    np += __popcll(bp);
-    nj += __popcll(bj);
-  }
-  if (lane == 0) {
-    a.pos_cnt[q] = np;
-    a.junk_cnt[q] = nj;
-  }
-}
-
-// ---- b) fused distance + rank counts --------------------------------------------
 struct RankH2Args {
-  int S, tps, tiles_n;            // segments, gallery tiles per segment, gallery tiles
-  int64_t items;                  // panels * S
+  FusedPlan plan;
   int64_t g_offset;
   int Ptot;
   const float* sorted_d;          // [Q][Ptot]
@@ -193,17 +82,12 @@ __device__ inline float uniform_f32(float x) {
 template <int BM, int BN, int WM, int WN, int NS, int KEY>
 __global__ void __launch_bounds__(64 * WM * WN)
 rank_count_h2_kernel(GemmParams p, RankH2Args a) {
-  using T = H2Tile<BM, BN, WM, WN, NS>;
-  constexpr int NW = T::NW, TM = T::TM, TN = T::TN, HB = T::HB;
-  constexpr int WCOLS = BN / WN;
-  constexpr int BNH = BN / HB, LD = BNH + 4;
-  constexpr int RPW = BM / NW;             // rows a wave finishes
-  constexpr int CS = (BNH + 63) / 64;      // columns per lane and pass
-  static_assert(BM % NW == 0 && RPW <= 64, "rows per wave");
-  static_assert(BNH % WCOLS == 0, "a wave's columns fall in one pass");
-  constexpr int STATE = T::LDS_BYTES;      // row state beside the stages / the parked tile
+  using F = FusedTile<BM, BN, WM, WN, NS>;
+  constexpr int NW = F::NW, TM = F::TM, TN = F::TN, HB = F::HB;
+  constexpr int BNH = F::BNH, RPW = F::RPW, CS = F::CS, STATE = F::STATE;
+  static_assert(RPW <= 64, "a lane per row sets the row state up");
   constexpr int NB = 4, PB = 64 * NB;      // positives binned per round: NB registers a lane
-  static_assert(STATE % 16 == 0 && STATE + BM * 16 + NW * PB * 4 <= kLdsBytesGfx950, "LDS");
+  static_assert(STATE + BM * 16 + NW * PB * 4 <= kLdsBytesGfx950, "LDS");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[STATE + BM * 16 + NW * PB * 4];
   float* s_df = reinterpret_cast<float*>(lds + STATE);   // first positive's distance
   float* s_dmax = s_df + BM;                             // last positive's
@@ -214,8 +98,6 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave / WN, wn = wave - wm * WN;
-  const int r16 = lane & 15, h = lane >> 4;
-  const int wc0 = wn * WCOLS;
   const int Ptot = a.Ptot;
   // this wave's block of a row's sorted positives, PB floats (+inf past the list)
   float* s_S = reinterpret_cast<float*>(lds + STATE + BM * 16) + wave * PB;
@@ -227,11 +109,9 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
     }
   };
 
-  for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
-    const int panel = (int)(item / a.S), s = (int)(item - (int64_t)panel * a.S);
-    const int m0 = panel * BM;
-    const int mrem = p.M - m0;
-    const int t0 = s * a.tps, t1 = min(t0 + a.tps, a.tiles_n);
+  for (int64_t item = blockIdx.x; item < a.plan.items; item += gridDim.x) {
+    const FusedItem it = fused_item(a.plan, item, p.M, BM);
+    const int m0 = it.m0, mrem = it.mrem;
     // the state of this wave's rows (only this wave touches it)
     if (lane < RPW) {
       const int row = wave * RPW + lane;
@@ -248,32 +128,22 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
       s_P[row] = P;
     }
 
-    for (int tn = t0; tn < t1; ++tn) {
+    for (int tn = it.t0; tn < it.t1; ++tn) {
       const int n0 = tn * BN;
-      const int nrem = p.Ncol - n0;
       f32x4 acc[TM][TN];
       h2_kloop<BM, BN, WM, WN, NS>(p, lds, m0, n0, wave, lane, wm, wn, acc);
 
 #pragma unroll
       for (int hb = 0; hb < HB; ++hb) {
         const int c0h = hb * BNH;
-        __syncthreads();  // the stages / the previous pass are no longer read
-        if (wc0 >= c0h && wc0 < c0h + BNH) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            const int row = wm * (BM / WM) + i * 16 + r16;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-              const int col = wc0 - c0h + j * 16 + 4 * h;
-              *reinterpret_cast<f32x4*>(t + row * LD + col) = acc[i][j];
-            }
-          }
-        }
-        __syncthreads();
-        // this lane's columns of the pass: norms and scales once for all rows
+        fused_park<F>(t, acc, hb, wm, wn, lane);
+        // fused_cols written out, with the camera beside the norm and the scale:
+        // through the shared piece the 192 x 192 instantiations spill two / one
+        // more SGPRs
         bool ok[CS];
         float gn[CS], rb[CS];
         int cam[CS];
+        const int nrem = p.Ncol - n0;
 #pragma unroll
         for (int j = 0; j < CS; ++j) {
           const int c = j * 64 + lane;
@@ -301,10 +171,7 @@ rank_count_h2_kernel(GemmParams p, RankH2Args a) {
           int nh = 0;
 #pragma unroll
           for (int j = 0; j < CS; ++j) {
-            const int c = j * 64 + lane;
-            // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
-            const float dot = ok[j] ? t[row * LD + c] : 0.f;
-            d[j] = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
+            d[j] = fused_cell<F>(p, t, row, j * 64 + lane, ok[j], qn, ra, gn[j], rb[j]);
             hit[j] = ok[j] && d[j] <= dmax;   // d > dmax: ordered after every positive
             if (KEY == kBinKeyCam) hit[j] = hit[j] && cam[j] != qc;
             nh += __popcll(__ballot(hit[j]));
@@ -458,8 +325,7 @@ cmc_h2_junk_kernel(int64_t Q, int Ptot, const float* __restrict__ sorted_d,
 
 template <int BM, int BN, int WM, int WN, int NS, int KEY>
 static int launch_rank_count(const GemmParams& p, const RankH2Args& a, hipStream_t st) {
-  const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
-  hipLaunchKernelGGL((rank_count_h2_kernel<BM, BN, WM, WN, NS, KEY>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((rank_count_h2_kernel<BM, BN, WM, WN, NS, KEY>), dim3(fused_grid(a.plan)),
                      dim3(64 * WM * WN), 0, st, p, a);
   PPS_CHECK_LAUNCH("rank_count_h2_kernel");
   return PPS_OK;
@@ -473,47 +339,53 @@ static int launch_rank_count_tile(int tile, const GemmParams& p, const RankH2Arg
                    : launch_rank_count<256, 256, 2, 4, 2, KEY>(p, a, st);
 }
 
-// The plan and the operands the two count entries share (their guards passed).
-static void rank_count_plan(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
-                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
-                            int D, int metric, int64_t g_offset, int Ptot,
-                            const float* sorted_d, const int32_t* sorted_idx,
-                            const int32_t* pos_total, int segments, int tile, int32_t* hist,
-                            GemmParams& p, RankH2Args& a) {
-  int BM, BN;
-  search_tile_shape(tile, BM, BN);
-  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
-  const int64_t panels = cdiv(Q, BM), tiles_n = cdiv(G, BN);
-  const int64_t S0 = fused_segments(Q, G, segments, BM, BN);
-  a.tiles_n = (int)tiles_n;
-  a.tps = (int)cdiv(tiles_n, S0);
-  a.S = (int)cdiv(tiles_n, a.tps);   // no empty segment
-  a.items = panels * a.S;
-  a.g_offset = g_offset;
-  a.Ptot = Ptot;
-  a.sorted_d = sorted_d; a.sorted_idx = sorted_idx; a.pos_total = pos_total;
-  a.hist = hist;
-
-  p.splitk = 1;
-  p.tiled = 3;
-  p.a3 = q2t; p.a_plane = Qp * D; p.a_bytes = (uint32_t)(2 * Qp * D * 2);
-  p.M = (int)Q;
-  p.b3 = g2t; p.b_plane = Gp * D; p.b_bytes = (uint32_t)(2 * Gp * D * 2);
-  p.Ncol = (int)G;
-  p.Kloop = D;
-  p.norm_a = qsq; p.norm_b = gsq;
-  p.rs_a = qrs; p.rs_b = grs;
-  p.metric = metric;
+// What the two count entries take alike (pps_abi.h), their shared guards and,
+// once those passed, the kernel's arguments.
+struct CountCall {
+  const uint16_t* q2t; int64_t Q; const float* qsq; const float* qrs;
+  const uint16_t* g2t; const float* gsq; const float* grs; int64_t G;
+  int D, metric;
+  int64_t g_offset;
+  int Ptot;
+  const float* sorted_d; const int32_t* sorted_idx; const int32_t* pos_total;
+  int segments, tile;
+  int32_t* hist;
+};
+// filled by name from an entry's own parameters (both entries name them alike)
+#define PPS_COUNT_CALL(c)                                                                  \
+  CountCall c{};                                                                           \
+  c.q2t = q2t; c.Q = Q; c.qsq = qsq; c.qrs = qrs; c.g2t = g2t; c.gsq = gsq; c.grs = grs;   \
+  c.G = G; c.D = D; c.metric = metric; c.g_offset = g_offset; c.Ptot = Ptot;               \
+  c.sorted_d = sorted_d; c.sorted_idx = sorted_idx; c.pos_total = pos_total;               \
+  c.segments = segments; c.tile = tile; c.hist = hist
+static int rank_count_guards(const char* fn, const CountCall& c) {
+  PPS_ENFORCE_AS(fn, c.sorted_d && c.sorted_idx && c.pos_total && c.hist, "null pointer");
+  PPS_TRY(h2_operands_guard(fn, c.q2t, c.Q, c.qsq, c.qrs, c.g2t, c.gsq, c.grs, c.G, c.D,
+                            c.metric));
+  const int Ptot = c.Ptot;
+  const int64_t g_offset = c.g_offset, G = c.G;
+  PPS_ENFORCE_AS(fn, Ptot > 0, "bad shape");
+  PPS_ENFORCE_AS(fn, g_offset >= 0 && g_offset + G < (1ll << 31),
+                 "gallery indices must fit int32");
+  PPS_TRY(fused_plan_guard(fn, c.segments, c.tile));
+  if (c.Ptot > kRankH2MaxP) {
+    set_error(std::string(fn) + ": Ptot = " + std::to_string(c.Ptot) +
+              " merged positives per query, the fused count takes at most " +
+              std::to_string(kRankH2MaxP) + " (pps_rank_count_h2_max_p)");
+    return PPS_ERR_CAPACITY;
+  }
+  return PPS_OK;
 }
-
-// the checks the planes arguments share with pps_search_h2_tiled (same texts)
-#define PPS_ENFORCE_H2_PLANES(Q, G, D, metric)                                              \
-  PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");         \
-  PPS_ENFORCE(Q < (1ll << 31), "Q must fit int32");                                         \
-  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");                                \
-  PPS_ENFORCE(2 * ((Q + 15) / 16 * 16) * D * 2 < kMaxBufBytes &&                            \
-                  2 * ((G + 15) / 16 * 16) * D * 2 < kMaxBufBytes,                          \
-              "planes over 2 GiB")
+static void rank_count_plan(const CountCall& c, GemmParams& p, RankH2Args& a) {
+  int BM, BN;
+  search_tile_shape(c.tile, BM, BN);
+  a.plan = fused_plan(c.Q, c.G, fused_segments(c.Q, c.G, c.segments, BM, BN), BM, BN);
+  a.g_offset = c.g_offset;
+  a.Ptot = c.Ptot;
+  a.sorted_d = c.sorted_d; a.sorted_idx = c.sorted_idx; a.pos_total = c.pos_total;
+  a.hist = c.hist;
+  p = h2_params(c.q2t, c.Q, c.Q, c.qsq, c.qrs, c.g2t, c.G, c.gsq, c.grs, c.D, c.metric);
+}
 
 }  // namespace pps
 
@@ -527,81 +399,26 @@ int64_t pps_rank_count_h2_workspace_bytes(int64_t Q, int64_t G, int Ptot, int se
   return 0;   // counts go out as atomics: nothing is staged
 }
 
-int pps_collect_matches_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
-                           const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
-                           int D, int metric, const int32_t* qcam, const int32_t* gcam,
-                           const int32_t* members, const int32_t* q_beg, const int32_t* q_end,
-                           int64_t g_offset, int Pmax, float* pos_d, int32_t* pos_idx,
-                           int32_t* pos_cnt, int Jmax, float* junk_d, int32_t* junk_idx,
-                           int32_t* junk_cnt, void* stream) {
-  PPS_ENFORCE(qcam && gcam && members && q_beg && q_end && pos_d && pos_idx && pos_cnt &&
-                  junk_d && junk_idx && junk_cnt,
-              "null pointer");
-  PPS_ENFORCE_H2_PLANES(Q, G, D, metric);
-  PPS_ENFORCE(Pmax > 0 && Jmax > 0, "bad shape");
-  PPS_ENFORCE(g_offset >= 0 && g_offset + G < (1ll << 31), "gallery indices must fit int32");
-  if (Q == 0) return PPS_OK;
-  PPS_ENFORCE(q2t && qsq && qrs && (G == 0 || (g2t && gsq && grs)), "null pointer");
-  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
-  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
-  PairArgs a{};
-  a.q2t = reinterpret_cast<const unsigned char*>(q2t);
-  a.g2t = reinterpret_cast<const unsigned char*>(g2t);
-  a.q_plane = Qp * D * 2;
-  a.g_plane = Gp * D * 2;
-  a.qsq = qsq; a.qrs = qrs; a.gsq = gsq; a.grs = grs;
-  a.Q = Q;
-  a.nkc = D / 32;
-  a.metric = metric;
-  a.qcam = qcam; a.gcam = gcam; a.members = members; a.q_beg = q_beg; a.q_end = q_end;
-  a.g_offset = g_offset;
-  a.Pmax = Pmax; a.Jmax = Jmax;
-  a.pos_d = pos_d; a.pos_idx = pos_idx; a.pos_cnt = pos_cnt;
-  a.junk_d = junk_d; a.junk_idx = junk_idx; a.junk_cnt = junk_cnt;
-  hipStream_t st = as_stream(stream);
-  const unsigned grid = (unsigned)((Q + kPairWaves - 1) / kPairWaves);
-  hipLaunchKernelGGL(collect_matches_h2_kernel, dim3(grid), dim3(64 * kPairWaves), 0, st, a);
-  PPS_CHECK_LAUNCH("collect_matches_h2_kernel");
-  return PPS_OK;
-}
-
+// workspace / ws_bytes: pps_rank_count_h2_workspace_bytes is 0, nothing to check
 int pps_rank_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
                             const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
                             int D, int metric, int64_t g_offset, int Ptot,
                             const float* sorted_d, const int32_t* sorted_idx,
                             const int32_t* pos_total, int Jmax, const float* junk_d,
                             const int32_t* junk_idx, const int32_t* junk_cnt, int segments,
-                            int tile, void* workspace, int64_t ws_bytes, int32_t* hist,
-                            int32_t* before, void* stream) {
-  PPS_ENFORCE(sorted_d && sorted_idx && pos_total && junk_d && junk_idx && junk_cnt && hist &&
-                  before,
-              "null pointer");
-  PPS_ENFORCE_H2_PLANES(Q, G, D, metric);
-  PPS_ENFORCE(Ptot > 0 && Jmax > 0, "bad shape");
-  PPS_ENFORCE(g_offset >= 0 && g_offset + G < (1ll << 31), "gallery indices must fit int32");
-  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
-  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
-              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
-  if (Ptot > kRankH2MaxP) {
-    set_error("pps_rank_count_h2_tiled: Ptot = " + std::to_string(Ptot) +
-              " merged positives per query, the fused count takes at most " +
-              std::to_string(kRankH2MaxP) + " (pps_rank_count_h2_max_p)");
-    return PPS_ERR_CAPACITY;
-  }
-  (void)workspace;   // pps_rank_count_h2_workspace_bytes is 0: nothing to check
-  (void)ws_bytes;
+                            int tile, void*, int64_t, int32_t* hist, int32_t* before,
+                            void* stream) {
+  PPS_COUNT_CALL(c);
+  PPS_ENFORCE(junk_d && junk_idx && junk_cnt && before, "null pointer");
+  PPS_ENFORCE(Jmax > 0, "bad shape");
+  PPS_TRY(rank_count_guards(__func__, c));
   if (Q == 0 || G == 0) return PPS_OK;
-  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
-  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
-
   GemmParams p{};
   RankH2Args a{};
-  rank_count_plan(q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, g_offset, Ptot, sorted_d,
-                  sorted_idx, pos_total, segments, tile, hist, p, a);
+  rank_count_plan(c, p, a);
   a.before = before;
-  const int rc = launch_rank_count_tile<kBinDist>(tile, p, a, st);
-  if (rc != PPS_OK) return rc;
+  PPS_TRY(launch_rank_count_tile<kBinDist>(tile, p, a, st));
   const unsigned grid = (unsigned)((Q + kJunkWaves - 1) / kJunkWaves);
   hipLaunchKernelGGL(rank_h2_junk_kernel, dim3(grid), dim3(64 * kJunkWaves), 0, st, Q, Ptot,
                      sorted_d, sorted_idx, pos_total, Jmax, junk_d, junk_idx, junk_cnt, hist,
@@ -616,40 +433,22 @@ int pps_cmc_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, con
                            const float* sorted_d, const int32_t* sorted_idx,
                            const int32_t* pos_total, const int32_t* qcam, const int32_t* gcam,
                            int Jmax, const float* junk_d, const int32_t* junk_idx,
-                           const int32_t* junk_cnt, int segments, int tile,
-                           void* workspace, int64_t ws_bytes, int32_t* hist, void* stream) {
-  PPS_ENFORCE(sorted_d && sorted_idx && pos_total && hist, "null pointer");
+                           const int32_t* junk_cnt, int segments, int tile, void*, int64_t,
+                           int32_t* hist, void* stream) {
+  PPS_COUNT_CALL(c);
   PPS_ENFORCE((qcam == nullptr) == (gcam == nullptr),
               "qcam and gcam are given together (separate_camera_set) or not at all");
   PPS_ENFORCE(gcam || (junk_d && junk_idx && junk_cnt && Jmax > 0),
               "without separate_camera_set the junk lists are required");
-  PPS_ENFORCE_H2_PLANES(Q, G, D, metric);
-  PPS_ENFORCE(Ptot > 0, "bad shape");
-  PPS_ENFORCE(g_offset >= 0 && g_offset + G < (1ll << 31), "gallery indices must fit int32");
-  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
-  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
-              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
-  if (Ptot > kRankH2MaxP) {
-    set_error("pps_cmc_count_h2_tiled: Ptot = " + std::to_string(Ptot) +
-              " merged positives per query, the fused count takes at most " +
-              std::to_string(kRankH2MaxP) + " (pps_rank_count_h2_max_p)");
-    return PPS_ERR_CAPACITY;
-  }
-  (void)workspace;   // pps_rank_count_h2_workspace_bytes is 0: nothing to check
-  (void)ws_bytes;
+  PPS_TRY(rank_count_guards(__func__, c));
   if (Q == 0 || G == 0) return PPS_OK;
-  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
-  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
-
   GemmParams p{};
   RankH2Args a{};
-  rank_count_plan(q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, g_offset, Ptot, sorted_d,
-                  sorted_idx, pos_total, segments, tile, hist, p, a);
+  rank_count_plan(c, p, a);
   a.qcam = qcam; a.gcam = gcam;
   if (gcam) return launch_rank_count_tile<kBinKeyCam>(tile, p, a, st);
-  const int rc = launch_rank_count_tile<kBinKey>(tile, p, a, st);
-  if (rc != PPS_OK) return rc;
+  PPS_TRY(launch_rank_count_tile<kBinKey>(tile, p, a, st));
   const unsigned grid = (unsigned)((Q + kJunkWaves - 1) / kJunkWaves);
   hipLaunchKernelGGL(cmc_h2_junk_kernel, dim3(grid), dim3(64 * kJunkWaves), 0, st, Q, Ptot,
                      sorted_d, sorted_idx, pos_total, Jmax, junk_d, junk_idx, junk_cnt, hist);

@@ -63,6 +63,56 @@ inline int64_t fused_segments(int64_t Q, int64_t G, int segments, int BM, int BN
   return S < tiles_n ? S : tiles_n;
 }
 
+// ---- chunk-tiled f16x2 operands: their GemmParams and the entry points' guards ---
+// f16 elements of one plane of an operand of `rows` rows (padded to 16), and
+// the bytes of its two planes
+inline int64_t h2_plane_elems(int64_t rows, int D) { return (rows + 15) / 16 * 16 * D; }
+inline int64_t h2_planes_bytes(int64_t rows, int D) { return 2 * h2_plane_elems(rows, D) * 2; }
+// The first M rows of an a operand whose planes hold Arows rows against the N
+// rows of a b operand (a cell's bits do not depend on the rows around it).
+inline GemmParams h2_params(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
+                            const float* ars, const uint16_t* b2t, int64_t N, const float* bsq,
+                            const float* brs, int D, int metric, float* out = nullptr,
+                            int64_t ldo = 0, int sym = 0) {
+  GemmParams p{};
+  p.splitk = 1;
+  p.tiled = 3;
+  p.a3 = a2t; p.a_plane = h2_plane_elems(Arows, D);
+  p.a_bytes = (uint32_t)h2_planes_bytes(Arows, D);
+  p.M = (int)M;
+  p.b3 = b2t; p.b_plane = h2_plane_elems(N, D);
+  p.b_bytes = (uint32_t)h2_planes_bytes(N, D);
+  p.Ncol = (int)N;
+  p.Kloop = D;
+  p.norm_a = asq; p.norm_b = bsq;
+  p.rs_a = ars; p.rs_b = brs;
+  p.out = out; p.ldo = ldo; p.metric = metric; p.sym = sym;
+  return p;
+}
+// The checks of two plane operands of Q and G rows (fn: the entry point's
+// name).  The pointers are looked at only when both operands have rows: an
+// entry returns early on an empty one, which may come with null pointers.
+inline int h2_operands_guard(const char* fn, const uint16_t* q2t, int64_t Q, const float* qsq,
+                             const float* qrs, const uint16_t* g2t, const float* gsq,
+                             const float* grs, int64_t G, int D, int metric) {
+  PPS_ENFORCE_AS(fn, Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
+  PPS_ENFORCE_AS(fn, Q < (1ll << 31), "Q must fit int32");
+  PPS_ENFORCE_AS(fn, metric >= 0 && metric <= 2, "unknown metric");
+  PPS_ENFORCE_AS(fn, h2_planes_bytes(Q, D) < kMaxBufBytes && h2_planes_bytes(G, D) < kMaxBufBytes,
+                 "planes over 2 GiB");
+  if (Q == 0 || G == 0) return PPS_OK;
+  PPS_ENFORCE_AS(fn, q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
+  PPS_ENFORCE_AS(fn, aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  return PPS_OK;
+}
+// segments / tile of the fused kernels' work list
+inline int fused_plan_guard(const char* fn, int segments, int tile) {
+  PPS_ENFORCE_AS(fn, segments >= 0, "segments must be >= 0 (0 = auto)");
+  PPS_ENFORCE_AS(fn, tile >= 0 && tile < kSearchNumTiles,
+                 "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
+  return PPS_OK;
+}
+
 // ---- fused f16x2 entries other translation units call --------------------------
 // byte offset of row r's chunk 0, slot s within a chunk-tiled f16 plane:
 // [r / 16][kc][r % 16][32]

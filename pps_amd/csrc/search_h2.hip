@@ -1,14 +1,12 @@
 // Fused f16x2 distance + stable top-k ("search"): the k nearest gallery rows
 // of every query without the [Q, G] distance matrix.
 //
-// Work item = (query panel of BM rows, gallery segment s of S).  A workgroup
-// walks the BN-column tiles of its segment; per tile it runs the K loop of
-// gemm_h2_kernel (h2_kloop: chunks ascending, mfma_h2t's three terms, f32
-// accumulation), parks the accumulators in LDS like h2_dist_epilogue and
-// finishes each distance with the same expression,
-//   dist_value(p, (acc * rs_a) * rs_b, qn, gn),
-// so every value has the bits pps_distmat_h2_tiled would have written.
-// Instead of storing them, each wave filters its rows of the parked tile:
+// This file holds search_h2_kernel -- the fused frame of h2_fused_common.hpp
+// (work item = query panel x gallery segment, h2_kloop per tile, the
+// accumulators parked in LDS, fused_cell finishing each distance with the bits
+// pps_distmat_h2_tiled would have written) around a top-k filter -- its host
+// plan and workspace layout, and the three search entry points.
+// Instead of storing the distances, each wave filters its rows of the parked tile:
 // a column survives if its packed (float_key(d) << 32 | column) value is not
 // above the row's threshold and is appended to the row's candidate buffer;
 // when the next pass could overflow the buffer the wave cuts it back to
@@ -36,8 +34,7 @@
 // candidate buffers live in the caller's workspace.
 #include <algorithm>
 
-#include "gemm_h2_common.hpp"
-#include "retrieval.hpp"
+#include "h2_fused_common.hpp"
 #include "topk_wave_common.hpp"
 
 namespace pps {
@@ -51,8 +48,7 @@ constexpr int kSearchJ = search_cap(kTkwMaxK) / 64;   // registers per lane of a
 
 struct SearchArgs {
   int k, cap;
-  int S, tps, tiles_n;            // segments, gallery tiles per segment, gallery tiles
-  int64_t items;                  // panels * S
+  FusedPlan plan;
   unsigned long long* cand;       // [slots][BM][cap]
   float* pvals;                   // [S][Q][k]
   int32_t* pidx;
@@ -93,18 +89,13 @@ __device__ inline unsigned long long uniform_u64(unsigned long long x) {
 template <int BM, int BN, int WM, int WN, int NS, bool EXCL, bool ROWMAX = false>
 __global__ void __launch_bounds__(64 * WM * WN)
 search_h2_kernel(GemmParams p, SearchArgs a) {
-  using T = H2Tile<BM, BN, WM, WN, NS>;
-  constexpr int NW = T::NW, TM = T::TM, TN = T::TN, HB = T::HB;
-  constexpr int WCOLS = BN / WN;
-  constexpr int BNH = BN / HB, LD = BNH + 4;
-  constexpr int RPW = BM / NW;             // rows a wave filters
-  constexpr int CS = (BNH + 63) / 64;      // columns per lane and pass
-  static_assert(BM % NW == 0 && BM <= kSearchMaxBM, "rows per wave / slot rows");
+  using F = FusedTile<BM, BN, WM, WN, NS>;
+  constexpr int NW = F::NW, TM = F::TM, TN = F::TN, HB = F::HB;
+  constexpr int BNH = F::BNH, RPW = F::RPW, CS = F::CS, STATE = F::STATE;
+  static_assert(BM <= kSearchMaxBM, "slot rows");
   static_assert(BNH <= kSearchInflow, "a pass's inflow is what search_cap leaves room for");
-  static_assert(BNH % WCOLS == 0, "a wave's columns fall in one pass");
-  static_assert(NW * kTkwMaxK * 8 <= T::LDS_BYTES, "sort scratch of the waves");
-  constexpr int STATE = T::LDS_BYTES;      // row state beside the stages / the parked tile
-  static_assert(STATE % 16 == 0 && STATE + BM * 16 <= kLdsBytesGfx950, "LDS");
+  static_assert(NW * kTkwMaxK * 8 <= F::LDS_BYTES, "sort scratch of the waves");
+  static_assert(STATE + BM * 16 <= kLdsBytesGfx950, "LDS");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[STATE + BM * 16];
   unsigned long long* s_thr = reinterpret_cast<unsigned long long*>(lds + STATE);
   int* s_n = reinterpret_cast<int*>(lds + STATE + BM * 8);
@@ -113,56 +104,32 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave / WN, wn = wave - wm * WN;
-  const int r16 = lane & 15, h = lane >> 4;
-  const int wc0 = wn * WCOLS;
   const int k = a.k, cap = a.cap;
   unsigned long long* cand = a.cand + (int64_t)blockIdx.x * BM * cap;
   unsigned long long* sbuf = reinterpret_cast<unsigned long long*>(lds) + wave * kTkwMaxK;
 
-  for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
-    const int panel = (int)(item / a.S), s = (int)(item - (int64_t)panel * a.S);
-    const int m0 = panel * BM;
-    const int mrem = p.M - m0;
-    const int t0 = s * a.tps, t1 = min(t0 + a.tps, a.tiles_n);
-    const int cbase = t0 * BN;   // the segment's first gallery column
+  for (int64_t item = blockIdx.x; item < a.plan.items; item += gridDim.x) {
+    const FusedItem it = fused_item(a.plan, item, p.M, BM);
+    const int s = it.s, m0 = it.m0, mrem = it.mrem;
+    const int cbase = it.t0 * BN;   // the segment's first gallery column
     // the rows of this wave start empty (only this wave touches their state)
     for (int r = lane; r < RPW; r += 64) {
       s_thr[wave * RPW + r] = ~0ull;   // inclusive: entries <= thr stay candidates
       s_n[wave * RPW + r] = 0;
     }
 
-    for (int tn = t0; tn < t1; ++tn) {
+    for (int tn = it.t0; tn < it.t1; ++tn) {
       const int n0 = tn * BN;
-      const int nrem = p.Ncol - n0;
       f32x4 acc[TM][TN];
       h2_kloop<BM, BN, WM, WN, NS>(p, lds, m0, n0, wave, lane, wm, wn, acc);
 
 #pragma unroll
       for (int hb = 0; hb < HB; ++hb) {
         const int c0h = hb * BNH;
-        __syncthreads();  // the stages / the previous pass are no longer read
-        if (wc0 >= c0h && wc0 < c0h + BNH) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            const int row = wm * (BM / WM) + i * 16 + r16;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-              const int col = wc0 - c0h + j * 16 + 4 * h;
-              *reinterpret_cast<f32x4*>(t + row * LD + col) = acc[i][j];
-            }
-          }
-        }
-        __syncthreads();
-        // this lane's columns of the pass: norms and scales once for all rows
+        fused_park<F>(t, acc, hb, wm, wn, lane);
         bool ok[CS];
         float gn[CS], rb[CS];
-#pragma unroll
-        for (int j = 0; j < CS; ++j) {
-          const int c = j * 64 + lane;
-          ok[j] = c < BNH && c0h + c < nrem;
-          gn[j] = ok[j] ? p.norm_b[n0 + c0h + c] : 0.f;
-          rb[j] = ok[j] ? p.rs_b[n0 + c0h + c] : 0.f;
-        }
+        fused_cols<F>(p, n0, hb, lane, ok, gn, rb);
         for (int i = 0; i < RPW; ++i) {
           const int row = wave * RPW + i;   // wave-uniform
           if (row >= mrem) break;
@@ -184,9 +151,7 @@ search_h2_kernel(GemmParams p, SearchArgs a) {
 #pragma unroll
           for (int j = 0; j < CS; ++j) {
             const int c = j * 64 + lane;
-            // two exact power-of-two scalings, row scale first (h2_dist_epilogue)
-            const float dot = ok[j] ? t[row * LD + c] : 0.f;
-            const float d = dist_value(p, (dot * ra) * rb[j], qn, gn[j]);
+            const float d = fused_cell<F>(p, t, row, c, ok[j], qn, ra, gn[j], rb[j]);
             if constexpr (ROWMAX) {
               if (ok[j]) mx = fmaxf(mx, fabsf(d));   // padded columns never count
             }
@@ -292,9 +257,8 @@ static SearchLayout search_layout(int64_t Q, int64_t G, int k, int segments) {
 
 template <int BM, int BN, int WM, int WN, int NS, bool EXCL, bool ROWMAX>
 static int launch_search(const GemmParams& p, SearchArgs a, hipStream_t st) {
-  const int64_t grid = std::min<int64_t>(a.items, kSearchSlots);
-  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS, EXCL, ROWMAX>), dim3((unsigned)grid),
-                     dim3(64 * WM * WN), 0, st, p, a);
+  hipLaunchKernelGGL((search_h2_kernel<BM, BN, WM, WN, NS, EXCL, ROWMAX>),
+                     dim3(fused_grid(a.plan)), dim3(64 * WM * WN), 0, st, p, a);
   PPS_CHECK_LAUNCH("search_h2_kernel");
   return PPS_OK;
 }
@@ -341,18 +305,12 @@ int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t
                          int tile, void* workspace, int64_t ws_bytes, float* vals,
                          int32_t* idx, const int32_t* q_group, const int32_t* g_group,
                          float* rowmax, void* stream) {
-  PPS_ENFORCE(vals && idx, "null pointer");
-  PPS_ENFORCE(!excl || (q_group && g_group), "null group pointer");
-  PPS_ENFORCE(Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
-  PPS_ENFORCE(Q < (1ll << 31), "Q must fit int32");
-  PPS_ENFORCE(metric >= 0 && metric <= 2, "unknown metric");
-  PPS_ENFORCE(k >= 1 && k <= kTkwMaxK, "k must be in [1, " + std::to_string(kTkwMaxK) + "]");
-  PPS_ENFORCE(segments >= 0, "segments must be >= 0 (0 = auto)");
-  PPS_ENFORCE(tile >= 0 && tile < kSearchNumTiles,
-              "search tile must be 0.." + std::to_string(kSearchNumTiles - 1));
-  const int64_t Qp = (Q + 15) / 16 * 16, Gp = (G + 15) / 16 * 16;
-  PPS_ENFORCE(2 * Qp * D * 2 < kMaxBufBytes && 2 * Gp * D * 2 < kMaxBufBytes,
-              "planes over 2 GiB");
+  PPS_ENFORCE_AS(fn, vals && idx, "null pointer");
+  PPS_ENFORCE_AS(fn, !excl || (q_group && g_group), "null group pointer");
+  PPS_TRY(h2_operands_guard(fn, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_ENFORCE_AS(fn, k >= 1 && k <= kTkwMaxK,
+                 "k must be in [1, " + std::to_string(kTkwMaxK) + "]");
+  PPS_TRY(fused_plan_guard(fn, segments, tile));
   if (Q == 0) return PPS_OK;
   hipStream_t st = as_stream(stream);
   if (G == 0) {  // nothing to rank: pad entries only
@@ -363,27 +321,20 @@ int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t
     PPS_CHECK_LAUNCH("search_fill_pad_kernel");
     return PPS_OK;
   }
-  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
-  PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
   const SearchLayout L = search_layout(Q, G, k, segments);
   if (!workspace || ws_bytes < L.total) {
     set_error(std::string(fn) + ": workspace of " + std::to_string(ws_bytes) + " bytes, need " +
               std::to_string(L.total));
     return PPS_ERR_CAPACITY;
   }
-  PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  PPS_ENFORCE_AS(fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
 
   int BM, BN;
   search_tile_shape(tile, BM, BN);
-  const int64_t panels = (Q + BM - 1) / BM, tiles_n = (G + BN - 1) / BN;
-  const int S0 = search_segments(Q, G, k, segments, BM, BN);
   SearchArgs a{};
   a.k = k;
   a.cap = search_cap(k);
-  a.tiles_n = (int)tiles_n;
-  a.tps = (int)((tiles_n + S0 - 1) / S0);
-  a.S = (int)((tiles_n + a.tps - 1) / a.tps);   // no empty segment
-  a.items = panels * a.S;
+  a.plan = fused_plan(Q, G, search_segments(Q, G, k, segments, BM, BN), BM, BN);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   a.cand = reinterpret_cast<unsigned long long*>(ws);
   a.pvals = reinterpret_cast<float*>(ws + L.cand_bytes);
@@ -393,25 +344,14 @@ int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t
   a.rowmax = reinterpret_cast<unsigned*>(rowmax);
   if (rowmax) (void)hipMemsetAsync(rowmax, 0, sizeof(float) * Q, st);   // the atomicMax's zero
 
-  GemmParams p{};
-  p.splitk = 1;
-  p.tiled = 3;
-  p.a3 = q2t; p.a_plane = Qp * D; p.a_bytes = (uint32_t)(2 * Qp * D * 2);
-  p.M = (int)Q;
-  p.b3 = g2t; p.b_plane = Gp * D; p.b_bytes = (uint32_t)(2 * Gp * D * 2);
-  p.Ncol = (int)G;
-  p.Kloop = D;
-  p.norm_a = qsq; p.norm_b = gsq;
-  p.rs_a = qrs; p.rs_b = grs;
-  p.metric = metric;
-
+  const GemmParams p = h2_params(q2t, Q, Q, qsq, qrs, g2t, G, gsq, grs, D, metric);
   const int rc = excl ? launch_search_tile<true, false>(tile, p, a, st)
                       : (rowmax ? launch_search_tile<false, true>(tile, p, a, st)
                                 : launch_search_tile<false, false>(tile, p, a, st));
   if (rc != PPS_OK) return rc;
   MergeOffsets offs{};
-  for (int s = 0; s < a.S; ++s) offs.off[s] = (int64_t)s * a.tps * BN;
-  return topk_merge(a.pvals, a.pidx, a.S, Q, k, offs, k, vals, idx, st);
+  for (int s = 0; s < a.plan.S; ++s) offs.off[s] = (int64_t)s * a.plan.tps * BN;
+  return topk_merge(a.pvals, a.pidx, a.plan.S, Q, k, offs, k, vals, idx, st);
 }
 
 int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,

@@ -494,6 +494,18 @@ def search_workspace_bytes(Q, G, k, segments=0):
     return n
 
 
+def _search_workspace(fn, workspace, need, device):
+    """The workspace tensor of a fused search: a new one of `need` bytes
+    (search_workspace_bytes), or the caller's if it holds that much."""
+    if workspace is None:
+        return torch.empty((need,), dtype=torch.uint8, device=device)
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
+            not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError('%s: workspace must be a contiguous device tensor of at least '
+                           '%d bytes (search_workspace_bytes)' % (fn, need))
+    return workspace
+
+
 def _pad_list(vals, idx, k):
     """[Q, kin] lists -> [Q, k], the tail (+inf, -1) (pps_topk_merge's pad)."""
     Q, kin = vals.shape
@@ -605,21 +617,13 @@ def _search_one(q, q_split, index, k, metric, segments, tile, workspace, q_group
             return topk_excluding(dist, k, q_group, g_group)
         vals, idx = topk(dist, kin)
         return _pad_list(vals, idx, k)
-    q2, qrs, qsq = q_split
-    g2, grs, gsq = index.h2
-    need = search_workspace_bytes(Q, G, k, segments)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=q.device)
-    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
-          not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise RuntimeError('search: workspace must be a contiguous device tensor of at least '
-                           '%d bytes (search_workspace_bytes)' % need)
+    workspace = _search_workspace('search', workspace,
+                                  search_workspace_bytes(Q, G, k, segments), q.device)
     vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
-    args = (_dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
-            _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
-            D, METRICS[metric], int(k), int(segments), int(tile), workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr())
+    args = _h2_operands('search', q_split, index) + (
+        METRICS[metric], int(k), int(segments), int(tile), workspace.data_ptr(),
+        workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr())
     if q_group is None:
         call('pps_search_h2_tiled', *(args + (_stream(),)))
     else:
@@ -872,19 +876,25 @@ def rank_count_h2_workspace_bytes(Q, G, Ptot, segments=0):
     return n
 
 
+def _h2_split_args(split, name):
+    """(planes, norms, scales) of a split_h2_tiled triple as the entry points
+    take them."""
+    x2, xrs, xsq = split
+    return (_dev(x2, name + '2t', torch.int16), _dev(xsq, name + 'sq'), _dev(xrs, name + 'rs'))
+
+
 def _h2_operands(fn, q_split, index):
-    """The ten leading arguments of the fused h2 entry points (queries' and
+    """The nine leading arguments of the fused h2 entry points (queries' and
     gallery's planes, norms, scales, shapes)."""
     if not isinstance(index, GalleryIndex) or index.h2 is None:
         raise RuntimeError('%s: the gallery must be a GalleryIndex holding an h2 split' % fn)
-    q2, qrs, qsq = q_split
-    g2, grs, gsq = index.h2
+    q2, qsq = q_split[0], q_split[2]
     Q, G, D = qsq.shape[0], index.shape[0], index.shape[1]
     if q2.dim() != 3 or q2.shape[2] != D or q2.shape[1] != (Q + 15) // 16 * 16:
         raise RuntimeError('%s: q_split %s does not fit %d queries of width %d'
                            % (fn, tuple(q2.shape), Q, D))
-    return (_dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'), _dev(qrs, 'qrs'),
-            _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G, D)
+    q = _h2_split_args(q_split, 'q')
+    return (q[0], Q) + q[1:] + _h2_split_args(index.h2, 'g') + (G, D)
 
 
 def _workspace_arg(fn, workspace):
@@ -1254,23 +1264,17 @@ def search_rowmax(q, index, k, metric='euclidean', segments=0, tile=0, workspace
     if D % 32 != 0 or not q.is_contiguous() or not 1 <= k <= search_max_k():
         raise RuntimeError('search_rowmax: needs contiguous queries, D %% 32 == 0 and '
                            '1 <= k <= %d' % search_max_k())
-    q2, qrs, qsq = split_h2_tiled(q)
-    g2, grs, gsq = index.h2
-    need = search_workspace_bytes(Q, G, k, segments)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=q.device)
-    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or
-          not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise RuntimeError('search_rowmax: workspace must be a contiguous device tensor of at '
-                           'least %d bytes (search_workspace_bytes)' % need)
+    q_split = split_h2_tiled(q)   # held to the launch: args are its tensors' addresses
+    args = _h2_operands('search_rowmax', q_split, index)
+    workspace = _search_workspace('search_rowmax', workspace,
+                                  search_workspace_bytes(Q, G, k, segments), q.device)
     vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
     rowmax = torch.empty((Q,), dtype=torch.float32, device=q.device)
-    call('pps_search_h2_tiled_rowmax', _dev(q2, 'q2t', torch.int16), Q, _dev(qsq, 'qsq'),
-         _dev(qrs, 'qrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), G,
-         D, METRICS[metric], k, int(segments), int(tile), workspace.data_ptr(),
-         workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr(),
-         rowmax.data_ptr(), _stream())
+    call('pps_search_h2_tiled_rowmax', *(args + (
+        METRICS[metric], k, int(segments), int(tile), workspace.data_ptr(),
+        workspace.numel() * workspace.element_size(), vals.data_ptr(), idx.data_ptr(),
+        rowmax.data_ptr(), _stream())))
     return vals, idx, rowmax
 
 
@@ -1358,15 +1362,14 @@ def re_ranking_from_features(x, Q, k1=20, k2=6, lambda_value=0.3, metric='euclid
     if not 0 < Q < N:
         raise RuntimeError('re_ranking_from_features: need 0 < Q < N, got Q=%r N=%d' % (Q, N))
     G = N - Q
-    x2, xrs, xsq = split_h2_tiled(x)
-    g2, grs, gsq = split_h2_tiled(x[Q:])
+    x_split, g_split = split_h2_tiled(x), split_h2_tiled(x[Q:])
     nbytes = rerank_rows_workspace_bytes(Q, G, k1, k2, features=True, segments=segments)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
     out = torch.empty((Q, G), dtype=torch.float32, device=x.device)
-    call('pps_re_ranking_features', _dev(x2, 'x2t', torch.int16), _dev(xsq, 'xsq'),
-         _dev(xrs, 'xrs'), _dev(g2, 'g2t', torch.int16), _dev(gsq, 'gsq'), _dev(grs, 'grs'), Q, G,
-         D, METRICS[metric], int(k1), int(k2), float(lambda_value), int(segments), int(tile),
-         int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())
+    operands = _h2_split_args(x_split, 'x') + _h2_split_args(g_split, 'g')
+    call('pps_re_ranking_features', *(operands + (
+        Q, G, D, METRICS[metric], int(k1), int(k2), float(lambda_value), int(segments), int(tile),
+        int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())))
     return out
 
 
