@@ -1,6 +1,6 @@
 // Op-level conv / GEMM implementations behind the pps_conv2d_* and
 // pps_gemm_splitk_batched* entry points (abi.hip) and the whole-network plan
-// (model.hip): validate ENFORCE-style, fill the launch parameters, enqueue.
+// (model_run.hip): validate ENFORCE-style, fill the launch parameters, enqueue.
 #include <string>
 
 #include "pps_internal.hpp"

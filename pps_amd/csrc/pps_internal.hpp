@@ -239,7 +239,7 @@ __host__ __device__ inline float h2_scale_of(float amax, float* inv) {
 
 // ---- op-level implementations behind the pps_conv* / pps_stem / pps_maxpool
 // entry points (conv_ops.hip, stem.hip, feature_ops.hip), with the activation-max
-// plumbing the whole-network plan uses (model.hip): amax_out (may be null)
+// plumbing the whole-network plan uses (model_run.hip): amax_out (may be null)
 // receives max|y| of the launch's output; w_rs != null selects the f16x2
 // arithmetic (two-plane chunk-tiled weights w, per-channel scales w_rs, the
 // input tensors' maxima amax_in / amax_in2)
