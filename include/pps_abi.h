@@ -642,6 +642,19 @@ int pps_pair_dist_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const flo
                      int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
                      void* stream);
 
+/* pps_pair_dist_h2 with the b-rows in two plane sets that are never
+ * concatenated: a list index < B0 names that row of the first b operand
+ * (b0_2t / b0sq / b0rs, B0 rows), any other index row (index - B0) of the
+ * second (b1_2t / b1sq / b1rs, B1 rows); an index outside [0, B0 + B1) is read
+ * as the nearest valid row.  Every cell has the bits pps_distmat_h2_tiled
+ * would write for that a-row and b-row.  Both b operands are checked as
+ * pps_pair_dist_h2's; B0 + B1 < 2^31; B0, B1 > 0 unless Q == 0. */
+int pps_pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                           const uint16_t* b0_2t, const float* b0sq, const float* b0rs, int64_t B0,
+                           const uint16_t* b1_2t, const float* b1sq, const float* b1rs, int64_t B1,
+                           int D, int metric, const int32_t* lists, const int32_t* counts, int cap,
+                           float* out, void* stream);
+
 /* Row-form k-reciprocal re-ranking: no buffer grows with N^2 (N = Q + G) and
  * G has no cap.  W[i][j] = the value pps_distmat_h2_tiled writes for a-row
  * x_i and b-row x_j of x = [queries; gallery]; rowmax[i] = max_j
@@ -682,6 +695,36 @@ int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* 
                             int64_t G, int D, int metric, int k1, int k2, double lambda_value,
                             int segments, int tile, int64_t g_window, void* workspace,
                             int64_t ws_bytes, float* out, void* stream);
+
+/* pps_re_ranking_features against a gallery prepared once: the result is bit
+ * for bit pps_re_ranking_features on the planes of x = [queries; gallery], but
+ * the queries' planes (q2t / qsq / qrs, Q rows) and the gallery's (g2t / gsq /
+ * grs, G rows) stay separate operands and the gallery-against-gallery search,
+ * which depends on no query, is the caller's:
+ *   nn_vals / nn_idx [G][nn_ld], g_rowmax [G]: vals / idx / rowmax of
+ *   pps_search_h2_tiled_rowmax of the gallery against itself with k >= k1 + 1
+ *   (nn_ld = that k; indices in gallery numbering).  A prefix of a stable
+ *   top-k list is the stable top-k' list, so one preparation serves every
+ *   smaller k1.  The call reads them only.
+ * Per call: three searches with k = k1 + 1 (q x q, g x q, q x g), one
+ * pps_topk_merge of the query-column and the gallery-column lists of all N
+ * rows (query columns carry the smaller global indices, so ties fall as in
+ * the one search over all columns), the elementwise max of the partial row
+ * maxima, pps_pair_dist_h2_parts for the weights, then the unchanged stages.
+ * Checks: pps_re_ranking_features's with each operand's planes under 2 GiB,
+ * plus nn_ld >= k1 + 1 and non-null nn_vals / nn_idx / g_rowmax; all before
+ * anything is launched.  The size function is host arithmetic, non-decreasing
+ * in Q and in G, -1 on bad arguments: pps_rerank_rows_workspace_bytes(Q, G)'s
+ * carves, the merge input (2 * 2 * N * (k1 + 1) * 4 bytes), Q floats, and one
+ * region that holds any of the three searches' workspaces. */
+int64_t pps_rerank_prepared_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments);
+int pps_re_ranking_prepared(const uint16_t* q2t, const float* qsq, const float* qrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t Q,
+                            int64_t G, int D, int metric, const float* nn_vals,
+                            const int32_t* nn_idx, int nn_ld, const float* g_rowmax, int k1,
+                            int k2, double lambda_value, int segments, int tile,
+                            int64_t g_window, void* workspace, int64_t ws_bytes, float* out,
+                            void* stream);
 
 /* ---- feature extractor ----------------------------------------------------
  * Implicit-GEMM convolution + test-mode SpatialBN + optional residual Sum +

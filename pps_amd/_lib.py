@@ -115,6 +115,12 @@ SIGNATURES = {
     'pps_re_ranking_features': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int,
                                 c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_i64, c_ptr,
                                 c_i64, c_ptr, c_ptr],
+    'pps_pair_dist_h2_parts': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                               c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr,
+                               c_ptr],
+    'pps_re_ranking_prepared': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int,
+                                c_int, c_ptr, c_ptr, c_int, c_ptr, c_int, c_int, ctypes.c_double,
+                                c_int, c_int, c_i64, c_ptr, c_i64, c_ptr, c_ptr],
     'pps_conv2d_bn_act': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int,
                           c_ptr, c_int, c_int, c_int, c_int, c_ptr],
@@ -218,6 +224,7 @@ EXTRA = {
                                        c_int, c_int], ctypes.c_int64),
     'pps_rerank_rows_workspace_bytes': ([c_i64, c_i64, c_int, c_int], ctypes.c_int64),
     'pps_rerank_features_workspace_bytes': ([c_i64, c_i64, c_int, c_int, c_int], ctypes.c_int64),
+    'pps_rerank_prepared_workspace_bytes': ([c_i64, c_i64, c_int, c_int, c_int], ctypes.c_int64),
     'pps_last_error': ([], ctypes.c_char_p),
     'pps_registered_ops': ([], ctypes.c_char_p),
     'pps_model_feat_dim': ([c_ptr], ctypes.c_int),

@@ -573,6 +573,35 @@ int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* 
                      ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
 }
 
+int64_t pps_rerank_prepared_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments) {
+  if (Q < 0 || G < 0 || k1 < 1 || k1 + 1 > 64 || k1 + 1 > kTkwMaxK || k2 < 1 || k2 > k1 + 1 ||
+      segments < 0)
+    return -1;
+  return rerank_prepared_workspace_bytes(Q, G, k1, k2, segments);
+}
+
+int pps_re_ranking_prepared(const uint16_t* q2t, const float* qsq, const float* qrs,
+                            const uint16_t* g2t, const float* gsq, const float* grs, int64_t Q,
+                            int64_t G, int D, int metric, const float* nn_vals,
+                            const int32_t* nn_idx, int nn_ld, const float* g_rowmax, int k1,
+                            int k2, double lambda_value, int segments, int tile,
+                            int64_t g_window, void* workspace, int64_t ws_bytes, float* out,
+                            void* stream) {
+  PPS_ENFORCE(workspace && out && nn_vals && nn_idx && g_rowmax, "null pointer");
+  PPS_TRY(rerank_rows_guards(__func__, Q, G, k1, k2, g_window));   // Q, G > 0, N in int32
+  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(fused_plan_guard(__func__, segments, tile));
+  PPS_ENFORCE(nn_ld >= k1 + 1, "nn_ld must be >= k1 + 1");
+  PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RrPrepared src{};
+  src.q2t = q2t; src.qsq = qsq; src.qrs = qrs;
+  src.g2t = g2t; src.gsq = gsq; src.grs = grs;
+  src.nn_vals = nn_vals; src.nn_idx = nn_idx; src.nn_ld = nn_ld; src.g_rowmax = g_rowmax;
+  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
+  return rerank_prepared(src, Q, G, k1, k2, lambda_value, g_window, workspace,
+                         ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
+}
+
 int pps_conv1x1_seam_x3(const float* x, int64_t M, int K1, const uint16_t* w2c, int N1,
                         const float* scale2c, const float* shift2c, const float* residual,
                         float* trunk, const uint16_t* w2a, int N2, const float* scale2a,

@@ -166,17 +166,37 @@ __device__ __forceinline__ const unsigned char* pair_a_frag(const PairOperands& 
 // lane >> 4, both planes; no LDS).  All 16 a-rows of the MFMA are the one row,
 // so every lane group holds a copy of a block's 16 dot products.  Call with
 // all lanes of the wave (MFMA).
-template <class RowOf>
-__device__ __forceinline__ float pair_dots(const PairOperands& a, const unsigned char* qa, int m0,
-                                           int end, int lane, RowOf row_of) {
+//
+// PARTS: the b-rows live in two plane sets -- row r < p.B0 is row r of a's b
+// operand, any other row is row r - p.B0 of p's -- so a block column carries
+// its own base and its own plane stride.  Nothing else differs: same loads,
+// same MFMA order, same bits.
+struct PairPart {   // the second b operand of the two-part form
+  const unsigned char* g2t;
+  int64_t g_plane;
+  const float* gsq; const float* grs;
+  int B0;           // rows of the first b operand
+};
+template <bool PARTS, class RowOf>
+__device__ __forceinline__ float pair_dots_impl(const PairOperands& a, const PairPart& p,
+                                                const unsigned char* qa, int m0, int end, int lane,
+                                                RowOf row_of) {
   const int r16 = lane & 15, slot = lane >> 4;
   const int nb = min(4, (end - m0 + 15) >> 4);   // blocks with an entry (wave-uniform)
   const unsigned char* ga[4];
+  int64_t gp[4];   // PARTS only
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     // columns past the list repeat its last entry (their cells are not read)
     const int mi = min(m0 + 16 * b + r16, end - 1);
-    ga[b] = a.g2t + h2_frag_off(row_of(mi), a.nkc, slot);
+    if constexpr (PARTS) {
+      const int r = row_of(mi);
+      const bool second = r >= p.B0;
+      ga[b] = (second ? p.g2t : a.g2t) + h2_frag_off(second ? r - p.B0 : r, a.nkc, slot);
+      gp[b] = second ? p.g_plane : a.g_plane;
+    } else {
+      ga[b] = a.g2t + h2_frag_off(row_of(mi), a.nkc, slot);
+    }
   }
   f32x4 acc[4];
 #pragma unroll
@@ -189,7 +209,9 @@ __device__ __forceinline__ float pair_dots(const PairOperands& a, const unsigned
     for (int b = 0; b < 4; ++b) {
       if (b < nb) {
         const f16x8 g0 = *reinterpret_cast<const f16x8*>(ga[b] + ko);
-        const f16x8 g1 = *reinterpret_cast<const f16x8*>(ga[b] + a.g_plane + ko);
+        int64_t plane = a.g_plane;
+        if constexpr (PARTS) plane = gp[b];
+        const f16x8 g1 = *reinterpret_cast<const f16x8*>(ga[b] + plane + ko);
         acc[b] = mfma_h2t(q0, q1, g0, g1, acc[b]);
       }
     }
@@ -203,6 +225,17 @@ __device__ __forceinline__ float pair_dots(const PairOperands& a, const unsigned
   const f32x4 t = rb4 == 0 ? acc[0] : rb4 == 1 ? acc[1] : rb4 == 2 ? acc[2] : acc[3];
   const float mine = re == 0 ? t[0] : re == 1 ? t[1] : re == 2 ? t[2] : t[3];
   return __shfl(mine, src);
+}
+template <class RowOf>
+__device__ __forceinline__ float pair_dots(const PairOperands& a, const unsigned char* qa, int m0,
+                                           int end, int lane, RowOf row_of) {
+  return pair_dots_impl<false>(a, PairPart{}, qa, m0, end, lane, row_of);
+}
+template <class RowOf>
+__device__ __forceinline__ float pair_dots_parts(const PairOperands& a, const PairPart& p,
+                                                 const unsigned char* qa, int m0, int end,
+                                                 int lane, RowOf row_of) {
+  return pair_dots_impl<true>(a, p, qa, m0, end, lane, row_of);
 }
 
 }  // namespace pps

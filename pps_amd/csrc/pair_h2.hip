@@ -5,7 +5,7 @@
 // order of the MFMA terms (chunks ascending, mfma_h2t's three terms), and the
 // finish is the same expression (h2_finish, h2_fused_common.hpp).
 //
-// Both kernels give one wave to an a-row and take its list 64 entries at a
+// The kernels give one wave to an a-row and take its list 64 entries at a
 // time through pair_dots (h2_fused_common.hpp), which hands lane i entry
 // m0 + i's dot product:
 //   collect_matches_h2_kernel  the list is the query's members (the MatchIndex
@@ -16,6 +16,9 @@
 //       out in list order.  Re-ranking's V-row weights (rerank.hip) are its
 //       first user: the distances of every row of x = [queries; gallery] to
 //       its few hundred expansion candidates.
+//   pair_dist_h2_parts_kernel  the same with the b-rows in two plane sets
+//       (queries' planes then the gallery's, never concatenated): re-ranking
+//       against a prepared gallery (rerank_prepared).
 #include "h2_fused_common.hpp"
 
 namespace pps {
@@ -118,6 +121,58 @@ int pair_dist_h2(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq
   return PPS_OK;
 }
 
+// pair_dist_h2_kernel with the b-rows in two plane sets (o's b operand holds
+// rows [0, B0), p's rows [B0, a.G)): the same walk, the entry's part choosing
+// the fragment base, the plane stride and the norm / scale source.
+__global__ void __launch_bounds__(64 * kPairWaves)
+pair_dist_h2_parts_kernel(PairOperands o, PairPart p, PairDistArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * kPairWaves + (threadIdx.x >> 6);
+  if (q >= o.Q) return;   // wave-uniform: every MFMA below runs with all lanes
+  int end = a.cap;
+  if (a.counts) end = min(max(__builtin_amdgcn_readfirstlane(a.counts[q]), 0), a.cap);
+  if (end == 0) return;
+  const int32_t* list = a.lists + q * a.cap;
+  const unsigned char* qa = pair_a_frag(o, (int)q, lane);
+  const float qn = o.qsq[q], ra = o.qrs[q];
+  GemmParams gp{};
+  gp.metric = o.metric;
+  // an index outside [0, B0 + B1) reads row 0 of the first part or the last of the second
+  auto row_of = [&](int e) { return min(max(list[e], 0), a.G - 1); };
+  for (int m0 = 0; m0 < end; m0 += 64) {
+    const float dot = pair_dots_parts(o, p, qa, m0, end, lane, row_of);
+    const int m = m0 + lane;
+    if (m < end) {
+      const int idx = row_of(m);
+      const bool second = idx >= p.B0;
+      const float* sq = second ? p.gsq : o.gsq;
+      const float* rs = second ? p.grs : o.grs;
+      const int r = second ? idx - p.B0 : idx;
+      a.out[q * a.cap + m] = h2_finish(gp, dot, ra, rs[r], qn, sq[r]);
+    }
+  }
+}
+
+int pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq,
+                       const float* qrs, const uint16_t* b0_2t, const float* b0sq,
+                       const float* b0rs, int64_t B0, const uint16_t* b1_2t, const float* b1sq,
+                       const float* b1rs, int64_t B1, int D, int metric, const int32_t* lists,
+                       const int32_t* counts, int cap, float* out, hipStream_t st) {
+  if (Q == 0 || B0 + B1 == 0 || cap == 0) return PPS_OK;
+  // an empty part is never addressed: the clamp keeps every index in the other
+  const PairOperands o = pair_operands(q2t, Q, Qrows, qsq, qrs, b0_2t, b0sq, b0rs, B0, D, metric);
+  PairPart p{};
+  p.g2t = reinterpret_cast<const unsigned char*>(b1_2t);
+  p.g_plane = h2_plane_elems(B1, D) * 2;
+  p.gsq = b1sq; p.grs = b1rs;
+  p.B0 = (int)B0;
+  const PairDistArgs a{(int)(B0 + B1), cap, lists, counts, out};
+  const unsigned grid = (unsigned)((Q + kPairWaves - 1) / kPairWaves);
+  hipLaunchKernelGGL(pair_dist_h2_parts_kernel, dim3(grid), dim3(64 * kPairWaves), 0, st, o, p, a);
+  PPS_CHECK_LAUNCH("pair_dist_h2_parts_kernel");
+  return PPS_OK;
+}
+
 // pps_distmat_h2_tiled's launch with the a planes' own plane stride
 int distmat_h2_head(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
                     const float* ars, const uint16_t* b2t, const float* bsq, const float* brs,
@@ -171,4 +226,20 @@ int pps_pair_dist_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const flo
   PPS_ENFORCE(G > 0, "a listed pair needs a b-row (G > 0)");
   return pair_dist_h2(q2t, Q, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, lists, counts, cap, out,
                       as_stream(stream));
+}
+
+int pps_pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
+                           const uint16_t* b0_2t, const float* b0sq, const float* b0rs, int64_t B0,
+                           const uint16_t* b1_2t, const float* b1sq, const float* b1rs, int64_t B1,
+                           int D, int metric, const int32_t* lists, const int32_t* counts, int cap,
+                           float* out, void* stream) {
+  PPS_ENFORCE(lists && out, "null pointer");
+  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, b0_2t, b0sq, b0rs, B0, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, b1_2t, b1sq, b1rs, B1, D, metric));
+  PPS_ENFORCE(B0 + B1 < (1ll << 31), "B0 + B1 must fit int32");
+  PPS_ENFORCE(cap >= 1, "cap must be >= 1");
+  if (Q == 0) return PPS_OK;
+  PPS_ENFORCE(B0 > 0 && B1 > 0, "a listed pair needs a b-row in each part (B0, B1 > 0)");
+  return pair_dist_h2_parts(q2t, Q, Q, qsq, qrs, b0_2t, b0sq, b0rs, B0, b1_2t, b1sq, b1rs, B1, D,
+                            metric, lists, counts, cap, out, as_stream(stream));
 }

@@ -23,6 +23,10 @@
 // steps 1-2 are the fused search with row maxima, step 3 is split into lists /
 // pair distances / weights, 4-5 run unchanged, 6 blends the q x g block in place
 // over gallery windows (no N x N buffer, no cap on G).
+// Prepared form (rerank_prepared): the row form with the queries'
+// and the gallery's planes as separate operands and the gallery rows'
+// gallery-column lists and maxima computed once by the caller -- steps 1-2 are
+// three small searches and a merge, the pair distances take a two-part b operand.
 #include <vector>
 
 #include "retrieval.hpp"
@@ -1153,12 +1157,55 @@ int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1,
   return (int64_t)RrRowsCarve(features, Q, G, k1, k2, segments).total;
 }
 
+// The stages every row-form pipeline runs the same way, from rank (and, for the
+// later ones, rowmax and the pair distances in v_val) in the carves:
+// 3a) the unique expansion lists
+static int rr_rows_lists(int64_t N, const RrLayout& L, const RrSparse& sp, hipStream_t st) {
+  const VRowsLds vl(L.K1, L.Kh);
+  const RrMatrix none{};
+  hipLaunchKernelGGL(rerank_v_rows_kernel<kVLists>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
+                     (const float*)nullptr, N, (int64_t)0, sp.rank, L.K1, L.Kh, L.vcap, vl.E2,
+                     sp.v_idx, sp.v_val, sp.v_cnt, none);
+  PPS_CHECK_LAUNCH_S("rerank_v_rows_kernel", st);
+  return PPS_OK;
+}
+// 3c) the weights from m[i][t] in v_val, then 4-5) unchanged
+static int rr_rows_weights_vqe(int64_t N, const RrLayout& L, int k2, const float* rowmax,
+                               const RrSparse& sp, hipStream_t st) {
+  hipLaunchKernelGGL(rerank_v_weights_kernel, dim3((unsigned)N), dim3(64), 0, st, rowmax, sp.v_cnt,
+                     L.vcap, sp.v_val);
+  PPS_CHECK_LAUNCH_S("rerank_v_weights_kernel", st);
+  return rr_vqe_csc(N, L, k2, sp, st);
+}
+// 6) the Jaccard pass over out = W[i][Q + g], blended in place
+static int rr_rows_blend(int64_t Q, int64_t G, const RrLayout& L, int k2, double lambda,
+                         int64_t g_window, const float* rowmax, const RrSparse& sp, float* out,
+                         hipStream_t st) {
+  const float lam = (float)lambda, one_m_lam = (float)(1.0 - lambda);
+  // windows: one when the gallery fits, else equal ones of at most kJacMaxWindow rows
+  int64_t wsize = g_window;
+  if (wsize <= 0) {
+    const int64_t nw = (G + kJacMaxWindow - 1) / kJacMaxWindow;
+    wsize = (G + nw - 1) / nw;
+  }
+  if (wsize > G) wsize = G;
+  const int64_t nwin = (G + wsize - 1) / wsize;
+  RrMatrix M{};
+  M.colmax = rowmax;
+  const int qc = k2 != 1 ? L.qcap : L.vcap;
+  hipLaunchKernelGGL(rerank_jaccard_kernel<kJacRows>, dim3((unsigned)Q, (unsigned)nwin),
+                     dim3(kJacThreads), jaccard_lds_bytes(wsize), st, Q, Q + G,
+                     (const float*)nullptr, (int64_t)0, M, sp.q_idx, sp.q_val, sp.q_cnt, qc,
+                     sp.start, sp.csc_row, sp.csc_val, lam, one_m_lam, out, wsize);
+  PPS_CHECK_LAUNCH_S("rerank_jaccard_kernel", st);
+  return PPS_OK;
+}
+
 int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
                 int64_t g_window, void* ws, size_t ws_bytes, float* out, hipStream_t st) {
-  const float lam = (float)lambda, one_m_lam = (float)(1.0 - lambda);
   const int64_t N = Q + G;
   const RrLayout L(k1, k2);
-  const int K1 = L.K1, Kh = L.Kh, vcap = L.vcap;
+  const int K1 = L.K1, vcap = L.vcap;
   const bool features = src.W == nullptr;
   const RrRowsCarve C(features, Q, G, k1, k2, src.segments);
   if (C.total > ws_bytes) {
@@ -1189,12 +1236,7 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
     if (rc != PPS_OK) return rc;
   }
   // 3) the unique expansion lists, their distances m[i][t], the weights
-  const VRowsLds vl(K1, Kh);
-  const RrMatrix none{};
-  hipLaunchKernelGGL(rerank_v_rows_kernel<kVLists>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
-                     (const float*)nullptr, N, (int64_t)0, sp.rank, K1, Kh, vcap, vl.E2, sp.v_idx,
-                     sp.v_val, sp.v_cnt, none);
-  PPS_CHECK_LAUNCH_S("rerank_v_rows_kernel", st);
+  PPS_TRY(rr_rows_lists(N, L, sp, st));
   if (features) {
     const int rc = pair_dist_h2(src.x2t, N, N, src.xsq, src.xrs, src.x2t, src.xsq, src.xrs, N,
                                 src.D, src.metric, sp.v_idx, sp.v_cnt, vcap, sp.v_val, st);
@@ -1204,12 +1246,8 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
                        sp.v_idx, sp.v_cnt, vcap, sp.v_val);
     PPS_CHECK_LAUNCH_S("rerank_gather_w_kernel", st);
   }
-  hipLaunchKernelGGL(rerank_v_weights_kernel, dim3((unsigned)N), dim3(64), 0, st, rowmax, sp.v_cnt,
-                     vcap, sp.v_val);
-  PPS_CHECK_LAUNCH_S("rerank_v_weights_kernel", st);
-  // 4-5) unchanged
-  const int rc45 = rr_vqe_csc(N, L, k2, sp, st);
-  if (rc45 != PPS_OK) return rc45;
+  // the weights; 4-5) unchanged
+  PPS_TRY(rr_rows_weights_vqe(N, L, k2, rowmax, sp, st));
   // 6) out = the q x g block W[i][Q + g]; the Jaccard pass blends it in place
   if (features) {
     const int rc = distmat_h2_head(src.x2t, Q, N, src.xsq, src.xrs, src.g2t, src.gsq, src.grs, G,
@@ -1219,23 +1257,113 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
     (void)hipMemcpy2DAsync(out, sizeof(float) * G, src.W + Q, sizeof(float) * src.ldw,
                            sizeof(float) * G, Q, hipMemcpyDeviceToDevice, st);
   }
-  // windows: one when the gallery fits, else equal ones of at most kJacMaxWindow rows
-  int64_t wsize = g_window;
-  if (wsize <= 0) {
-    const int64_t nw = (G + kJacMaxWindow - 1) / kJacMaxWindow;
-    wsize = (G + nw - 1) / nw;
+  return rr_rows_blend(Q, G, L, k2, lambda, g_window, rowmax, sp, out, st);
+}
+
+// ---- row form against a prepared gallery --------------------------
+// rowmax[i] = max(rowmax[i], other part's maximum): the query rows' from the
+// q x g search (rm_q), the gallery rows' from the preparation (g_rowmax).
+// Squares are >= 0 and max is exact: (W * W).amax(1) over all N columns.
+__global__ void rerank_rowmax_join_kernel(float* __restrict__ rowmax, const float* __restrict__ rm_q,
+                                          const float* __restrict__ g_rowmax, int64_t Q, int64_t N) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  rowmax[i] = fmaxf(rowmax[i], i < Q ? rm_q[i] : g_rowmax[i - Q]);
+}
+
+// rerank_rows' per-row carves, then the merge input (two lists [2][N][K1] of
+// values and of indices), the query rows' gallery-part maxima and one region
+// the three searches share (they run one after the other on the stream)
+struct RrPreparedCarve {
+  RrRowsCarve rows;
+  size_t mvals, midx, rm_q, search, total;
+  int64_t search_bytes;
+  RrPreparedCarve(int64_t Q, int64_t G, int k1, int k2, int segments)
+      : rows(false, Q, G, k1, k2, 0) {
+    const int64_t N = Q + G, K1 = k1 + 1;
+    size_t p = rows.total;
+    auto take = [&](size_t bytes) {
+      const size_t r = p;
+      p += (bytes + 255) / 256 * 256;
+      return r;
+    };
+    mvals = take(4 * 2 * N * K1);
+    midx = take(4 * 2 * N * K1);
+    rm_q = take(4 * Q);
+    search_bytes = std::max(search_h2_workspace_bound(Q, Q, (int)K1, segments),
+                            std::max(search_h2_workspace_bound(G, Q, (int)K1, segments),
+                                     search_h2_workspace_bound(Q, G, (int)K1, segments)));
+    search = take((size_t)search_bytes);
+    total = p;
   }
-  if (wsize > G) wsize = G;
-  const int64_t nwin = (G + wsize - 1) / wsize;
-  RrMatrix M{};
-  M.colmax = rowmax;
-  const int qc = k2 != 1 ? L.qcap : vcap;
-  hipLaunchKernelGGL(rerank_jaccard_kernel<kJacRows>, dim3((unsigned)Q, (unsigned)nwin),
-                     dim3(kJacThreads), jaccard_lds_bytes(wsize), st, Q, N, (const float*)nullptr,
-                     (int64_t)0, M, sp.q_idx, sp.q_val, sp.q_cnt, qc, sp.start, sp.csc_row,
-                     sp.csc_val, lam, one_m_lam, out, wsize);
-  PPS_CHECK_LAUNCH_S("rerank_jaccard_kernel", st);
-  return PPS_OK;
+};
+
+int64_t rerank_prepared_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments) {
+  return (int64_t)RrPreparedCarve(Q, G, k1, k2, segments).total;
+}
+
+int rerank_prepared(const RrPrepared& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
+                    int64_t g_window, void* ws, size_t ws_bytes, float* out, hipStream_t st) {
+  static const char* fn = "pps_re_ranking_prepared";
+  const int64_t N = Q + G;
+  const RrLayout L(k1, k2);
+  const int K1 = L.K1, vcap = L.vcap;
+  const RrPreparedCarve P(Q, G, k1, k2, src.segments);
+  const RrRowsCarve& C = P.rows;
+  if (P.total > ws_bytes) {
+    set_error("prepared rerank workspace too small: need " + std::to_string(P.total) + " bytes");
+    return PPS_ERR_CAPACITY;
+  }
+  char* base = reinterpret_cast<char*>(ws);
+  auto f32 = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+  auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
+  float* rowmax = f32(C.rowmax);
+  const RrSparse sp{i32(C.rank), i32(C.v_idx), f32(C.v_val), i32(C.v_cnt), i32(C.q_idx),
+                    f32(C.q_val), i32(C.q_cnt), i32(C.col_cnt), i32(C.start), i32(C.fill),
+                    i32(C.csc_row), f32(C.csc_val), i32(C.ovf_rows), i32(C.ovf_n)};
+  // 1-2) per row the stable top-K1 over the query columns (list 0, global
+  // offset 0) and over the gallery columns (list 1, offset Q); their stable
+  // merge is the top-K1 over all N columns
+  float* mv = f32(P.mvals);
+  int32_t* mi = i32(P.midx);
+  const int64_t l1 = N * K1;   // list 1 starts here
+  auto search = [&](const uint16_t* a2t, const float* asq, const float* ars, int64_t A,
+                    const uint16_t* b2t, const float* bsq, const float* brs, int64_t B,
+                    int64_t at, float* rm) {
+    return search_h2_tiled(fn, false, a2t, A, asq, ars, b2t, bsq, brs, B, src.D, src.metric, K1,
+                           src.segments, src.tile, base + P.search, P.search_bytes, mv + at,
+                           mi + at, nullptr, nullptr, rm, st);
+  };
+  PPS_TRY(search(src.q2t, src.qsq, src.qrs, Q, src.q2t, src.qsq, src.qrs, Q, 0, rowmax));
+  PPS_TRY(search(src.g2t, src.gsq, src.grs, G, src.q2t, src.qsq, src.qrs, Q, Q * K1, rowmax + Q));
+  PPS_TRY(search(src.q2t, src.qsq, src.qrs, Q, src.g2t, src.gsq, src.grs, G, l1, f32(P.rm_q)));
+  // the gallery rows' gallery-column lists: the first K1 of each prepared row
+  (void)hipMemcpy2DAsync(mv + l1 + Q * K1, sizeof(float) * K1, src.nn_vals,
+                         sizeof(float) * src.nn_ld, sizeof(float) * K1, G,
+                         hipMemcpyDeviceToDevice, st);
+  (void)hipMemcpy2DAsync(mi + l1 + Q * K1, sizeof(int32_t) * K1, src.nn_idx,
+                         sizeof(int32_t) * src.nn_ld, sizeof(int32_t) * K1, G,
+                         hipMemcpyDeviceToDevice, st);
+  MergeOffsets offs{};
+  offs.off[1] = Q;
+  PPS_TRY(topk_merge(mv, mi, 2, N, K1, offs, K1, f32(C.topv), sp.rank, st));
+  hipLaunchKernelGGL(rerank_rowmax_join_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st,
+                     rowmax, f32(P.rm_q), src.g_rowmax, Q, N);
+  PPS_CHECK_LAUNCH_S("rerank_rowmax_join_kernel", st);
+  // 3) the expansion lists name columns of [queries; gallery]: two-part pair
+  // distances, the query rows then the gallery rows
+  PPS_TRY(rr_rows_lists(N, L, sp, st));
+  PPS_TRY(pair_dist_h2_parts(src.q2t, Q, Q, src.qsq, src.qrs, src.q2t, src.qsq, src.qrs, Q,
+                             src.g2t, src.gsq, src.grs, G, src.D, src.metric, sp.v_idx, sp.v_cnt,
+                             vcap, sp.v_val, st));
+  PPS_TRY(pair_dist_h2_parts(src.g2t, G, G, src.gsq, src.grs, src.q2t, src.qsq, src.qrs, Q,
+                             src.g2t, src.gsq, src.grs, G, src.D, src.metric,
+                             sp.v_idx + Q * vcap, sp.v_cnt + Q, vcap, sp.v_val + Q * vcap, st));
+  PPS_TRY(rr_rows_weights_vqe(N, L, k2, rowmax, sp, st));
+  // 6) as rerank_rows
+  PPS_TRY(distmat_h2_head(src.q2t, Q, Q, src.qsq, src.qrs, src.g2t, src.gsq, src.grs, G, src.D,
+                          src.metric, out, G, st));
+  return rr_rows_blend(Q, G, L, k2, lambda, g_window, rowmax, sp, out, st);
 }
 
 }  // namespace pps

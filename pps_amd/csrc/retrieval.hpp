@@ -129,6 +129,9 @@ int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q, c
 // bytes that hold the workspace of a search of N rows against themselves, as a
 // bound that is non-decreasing in N (host arithmetic)
 int64_t search_h2_self_workspace_bound(int64_t N, int k, int segments);
+// search_h2.hip: the same for Q a-rows against G b-rows: at least the search's
+// workspace, non-decreasing in Q and in G
+int64_t search_h2_workspace_bound(int64_t Q, int64_t G, int k, int segments);
 // pair_h2.hip: out[r][t] = distance of a-row r to b-row lists[r][t], t <
 // min(counts[r], cap) (lists / out rows cap apart; counts null = cap each);
 // the a operand is the first Q rows of planes holding Qrows rows
@@ -136,6 +139,14 @@ int pair_dist_h2(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq
                  const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
                  int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
                  hipStream_t st);
+// pair_h2.hip: pair_dist_h2 with the b-rows in two plane sets: a list index
+// < B0 is that row of the first b operand, any other index row (index - B0) of
+// the second; indices are clamped to [0, B0 + B1)
+int pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq,
+                       const float* qrs, const uint16_t* b0_2t, const float* b0sq,
+                       const float* b0rs, int64_t B0, const uint16_t* b1_2t, const float* b1sq,
+                       const float* b1rs, int64_t B1, int D, int metric, const int32_t* lists,
+                       const int32_t* counts, int cap, float* out, hipStream_t st);
 // pair_h2.hip: the [M, N] block of the first M rows of an a operand holding
 // Arows rows against a whole b operand (pps_distmat_h2_tiled's launch and bits)
 int distmat_h2_head(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
@@ -224,6 +235,23 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
 // bytes of the workspace; features: the fused search's workspace included
 int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1, int k2,
                                     int segments);
+
+// Row form against a gallery prepared once: the queries' planes
+// and the gallery's are separate operands, and the gallery rows' top-(k1 + 1)
+// over the gallery columns (nn_vals / nn_idx, rows nn_ld apart, gallery
+// numbering) and their row maxima (g_rowmax) come from the caller -- one
+// pps_search_h2_tiled_rowmax of the gallery against itself, whatever the
+// queries.  Bit for bit rerank_rows on the planes of [queries; gallery].
+struct RrPrepared {
+  const uint16_t* q2t; const float* qsq; const float* qrs;   // Q rows
+  const uint16_t* g2t; const float* gsq; const float* grs;   // G rows
+  const float* nn_vals; const int32_t* nn_idx; int nn_ld;
+  const float* g_rowmax;
+  int D, metric, segments, tile;
+};
+int rerank_prepared(const RrPrepared& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
+                    int64_t g_window, void* ws, size_t ws_bytes, float* out, hipStream_t st);
+int64_t rerank_prepared_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments);
 
 // OD's arithmetic, float32 as NumPy does it (np.power(M, 2) then / colmax):
 // (m * m) / cm, both rounded (a product feeding a division cannot fuse), the

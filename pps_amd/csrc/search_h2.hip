@@ -283,6 +283,20 @@ int64_t search_h2_self_workspace_bound(int64_t N, int k, int segments) {
   return align256(slots * kSearchMaxBM * search_cap(k) * 8) + 2 * align256(entries * 4);
 }
 
+// The same bound for Q a-rows against G b-rows: at least
+// search_layout(Q, G, k, segments).total and non-decreasing in Q and in G.
+// S <= the gallery's tiles, <= kMergeMaxLists and <= the request; auto:
+// S <= 2 kSearchSlots / panels, so S * Q <= max(Q, 2^17).  Every term of the
+// min below grows with both arguments.
+int64_t search_h2_workspace_bound(int64_t Q, int64_t G, int k, int segments) {
+  const int64_t tq = std::max<int64_t>(cdiv(Q, 192), 1), tg = std::max<int64_t>(cdiv(G, 192), 1);
+  const int64_t slots = std::min<int64_t>(kSearchSlots, tq * tg);
+  const int64_t by_req = segments > 0 ? Q * std::min<int64_t>(segments, kMergeMaxLists)
+                                      : std::max<int64_t>(Q, 2 * kSearchSlots * kSearchMaxBM);
+  const int64_t entries = k * std::min<int64_t>(by_req, Q * std::min<int64_t>(tg, kMergeMaxLists));
+  return align256(slots * kSearchMaxBM * search_cap(k) * 8) + 2 * align256(entries * 4);
+}
+
 }  // namespace pps
 
 // ---- C ABI ----------------------------------------------------------------

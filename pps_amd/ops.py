@@ -1284,9 +1284,21 @@ def pair_dist(q, index, lists, counts=None, metric='euclidean'):
     min(counts[r], cap), with the bits compute_dist(q, index, math='h2',
     symmetric=False) holds at that cell; cells past a row's count are 0.
     lists [Q, cap] int32, counts [Q] int32 or None (every entry).  q: the
-    [Q, D] queries, or their split_h2_tiled triple."""
+    [Q, D] queries, or their split_h2_tiled triple.
+    index may be a pair (index0, index1) of h2 GalleryIndex that are never
+    concatenated (pps_pair_dist_h2_parts): a list index < G0 names that row of
+    index0, any other index row (index - G0) of index1; the bits are the same
+    kernel's at that cell."""
     q_split = q if isinstance(q, tuple) else split_h2_tiled(q)
-    args = _h2_operands('pair_dist', q_split, index)
+    parts = isinstance(index, (tuple, list))
+    if parts:
+        if len(index) != 2:
+            raise RuntimeError('pair_dist: a two-part gallery is (index0, index1)')
+        args = _h2_operands('pair_dist', q_split, index[0])
+        args1 = _h2_operands('pair_dist', q_split, index[1])
+        args = args[:8] + args1[4:]   # ..., B0, b1 planes / norms / scales, B1, D
+    else:
+        args = _h2_operands('pair_dist', q_split, index)
     Q = args[1]
     if lists.dim() != 2 or lists.shape[0] != Q or lists.shape[1] < 1:
         raise RuntimeError('pair_dist: lists must be [%d, cap >= 1]' % Q)
@@ -1294,7 +1306,7 @@ def pair_dist(q, index, lists, counts=None, metric='euclidean'):
     if counts is not None and tuple(counts.shape) != (Q,):
         raise RuntimeError('pair_dist: counts must be [%d]' % Q)
     out = torch.zeros((Q, cap), dtype=torch.float32, device=lists.device)
-    call('pps_pair_dist_h2', *(args + (
+    call('pps_pair_dist_h2_parts' if parts else 'pps_pair_dist_h2', *(args + (
         METRICS[metric], _dev(lists, 'lists', torch.int32),
         0 if counts is None else _dev(counts, 'counts', torch.int32), cap, out.data_ptr(),
         _stream())))
@@ -1350,7 +1362,8 @@ def re_ranking_from_features(x, Q, k1=20, k2=6, lambda_value=0.3, metric='euclid
     a row at k1 = 20, k2 = 6).  One h2 index only (x's planes under 2 GiB).
     Raises -- it never builds an [N, N] matrix silently -- when x is strided,
     D % 32 != 0 or the distance arithmetic is not h2: use re_ranking_rows on a
-    matrix of your own then."""
+    matrix of your own then.  For several query batches against one gallery,
+    RerankGallery gives the same bits without repeating the gallery's part."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise RuntimeError('re_ranking_from_features: x must be a [N, D] tensor')
     N, D = x.shape
@@ -1371,6 +1384,78 @@ def re_ranking_from_features(x, Q, k1=20, k2=6, lambda_value=0.3, metric='euclid
         Q, G, D, METRICS[metric], int(k1), int(k2), float(lambda_value), int(segments), int(tile),
         int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())))
     return out
+
+
+def rerank_prepared_workspace_bytes(Q, G, k1=20, k2=6, segments=0):
+    """Bytes of workspace of one RerankGallery.re_rank call (host arithmetic,
+    non-decreasing in Q and in G): re_ranking_rows' per-row structures, the
+    merge input and one region the three searches share."""
+    n = int(_lib.lib().pps_rerank_prepared_workspace_bytes(int(Q), int(G), int(k1), int(k2),
+                                                           int(segments)))
+    if n < 0:
+        raise RuntimeError('rerank_prepared_workspace_bytes: bad arguments Q=%r G=%r k1=%r k2=%r '
+                           'segments=%r' % (Q, G, k1, k2, segments))
+    return n
+
+
+class RerankGallery(object):
+    """A gallery prepared once for k-reciprocal re-ranking from the features
+    (DESIGN 6.1.6): re_rank(q) gives, bit for bit,
+    re_ranking_from_features(cat([q, gallery]), Q) for any number of query
+    batches, without repeating the gallery-against-gallery search and without
+    the planes of the concatenation.  gallery: a contiguous [G, D] tensor or an
+    h2 GalleryIndex.  Holds .index (the GalleryIndex), .k1, .metric and, from
+    one search_rowmax of the gallery against itself, .nn_vals / .nn_idx
+    ([G, k1 + 1], gallery numbering) and .rowmax ([G]); re_rank only reads
+    them.  Raises where re_ranking_from_features raises (strided features,
+    D % 32 != 0, distance arithmetic not h2): no matrix is built silently."""
+
+    def __init__(self, gallery, k1=20, metric='euclidean', segments=0, tile=0):
+        if isinstance(gallery, GalleryIndex):
+            index, ok = gallery, gallery.h2 is not None
+        else:
+            if not isinstance(gallery, torch.Tensor) or gallery.dim() != 2:
+                raise RuntimeError('RerankGallery: gallery must be a [G, D] tensor or a '
+                                   'GalleryIndex')
+            ok = gallery.is_contiguous() and gallery.shape[1] % 32 == 0
+            index = None
+        if not ok or dist_math() != 'h2':
+            raise RuntimeError('RerankGallery: needs contiguous features, D %% 32 == 0 and h2 '
+                               'distance arithmetic (math %r); re_ranking_rows takes a '
+                               'materialised matrix instead' % dist_math())
+        k1 = int(k1)
+        if not 1 <= k1 <= min(63, search_max_k() - 1):
+            raise RuntimeError('RerankGallery: k1 + 1 must be <= 64 and <= %d' % search_max_k())
+        self.index = index if index is not None else GalleryIndex(gallery, math='h2')
+        self.k1, self.metric = k1, metric
+        self.nn_vals, self.nn_idx, self.rowmax = search_rowmax(
+            self.index.feats, self.index, k1 + 1, metric=metric, segments=segments, tile=tile)
+
+    def re_rank(self, q, k1=None, k2=6, lambda_value=0.3, segments=0, tile=0, g_window=0):
+        """[Q, D] queries -> the re-ranked [Q, G] (pps_re_ranking_prepared).
+        k1 None = the prepared value; a smaller one reads a prefix of the
+        prepared lists, a larger one raises."""
+        k1 = self.k1 if k1 is None else int(k1)
+        if k1 > self.k1:
+            raise RuntimeError('RerankGallery.re_rank: k1=%d above the prepared k1=%d'
+                               % (k1, self.k1))
+        G, D = self.index.shape
+        if (not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] != D or
+                not q.is_contiguous() or q.shape[0] < 1):
+            raise RuntimeError('RerankGallery.re_rank: needs contiguous [Q >= 1, %d] queries; '
+                               're_ranking_rows takes a materialised matrix instead' % D)
+        Q = q.shape[0]
+        q_split = split_h2_tiled(q)   # held to the launch
+        nbytes = rerank_prepared_workspace_bytes(Q, G, k1, k2, segments)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        out = torch.empty((Q, G), dtype=torch.float32, device=q.device)
+        operands = _h2_split_args(q_split, 'q') + _h2_split_args(self.index.h2, 'g')
+        call('pps_re_ranking_prepared', *(operands + (
+            Q, G, D, METRICS[self.metric], _dev(self.nn_vals, 'nn_vals'),
+            _dev(self.nn_idx, 'nn_idx', torch.int32), self.nn_vals.shape[1],
+            _dev(self.rowmax, 'g_rowmax'), k1, int(k2), float(lambda_value), int(segments),
+            int(tile), int(g_window), ws.data_ptr(), nbytes, out.data_ptr(), _stream())))
+        return out
 
 
 def max_positives(qid, qcam, gid, gcam):

@@ -402,10 +402,12 @@ def evaluate(json_dataset, all_feats, output_dir, verbose=True):
 def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None,
                     rerank_from_features=False):
     """rerank_from_features: with cfg.REID.RERANK, the re-ranked single-query
-    and multi-query scores come from ops.re_ranking_from_features (row-form
-    re-ranking from the features: no [N, N] matrix, any gallery size) instead
-    of the self-distance matrix + ops.re_ranking.  One gallery index only; the
-    sharded evaluator keeps the matrix path."""
+    and multi-query scores have the bits of ops.re_ranking_from_features
+    (row-form re-ranking from the features: no [N, N] matrix, any gallery size)
+    instead of the self-distance matrix + ops.re_ranking -- through one
+    ops.RerankGallery, so the gallery-against-gallery search runs once for
+    both query sets.  One gallery index only; the sharded evaluator keeps the
+    matrix path."""
     metric = metric or cfg.REID.get('DISTANCE', 'euclidean')
     feat = _to_dev(all_feats)
     ids, cams, marks = np.asarray(ids), np.asarray(cams), np.asarray(marks)
@@ -471,7 +473,9 @@ def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None,
         with measure_time('Re-ranking distance...', verbose):
             # 16-byte rows: re-ranking reads the blocks in place (no N x N copy)
             if rerank_from_features:
-                rr = ops.re_ranking_from_features(torch.cat([qf, gf]), len(qi), metric=metric)
+                # the gallery's own neighbour lists once, for both query sets
+                rr_gallery = ops.RerankGallery(gsrc if tiled else gf, metric=metric)
+                rr = rr_gallery.re_rank(qf)
             elif whole:
                 rr = ops.re_ranking(q_g, q_q, g_g, symmetric=True, whole=True)
             else:
@@ -487,8 +491,7 @@ def evaluate_arrays(all_feats, ids, cams, marks, verbose=True, metric=None,
         if mq_inds.any():
             with measure_time('Multi Query, Re-ranking distance...', verbose):
                 if rerank_from_features:
-                    rr_mq = ops.re_ranking_from_features(torch.cat([pooled, gf]), len(pooled),
-                                                         metric=metric)
+                    rr_mq = rr_gallery.re_rank(pooled.contiguous())
                 else:
                     mq_mq = ops.compute_dist(pooled, pooled, metric=metric, pad_rows=True)
                     # g_g a block of the whole matrix: exactly symmetric, untagged
@@ -516,8 +519,16 @@ def re_ranking_from_features(query_feats, gallery_feats, k1=20, k2=6, lambda_val
                              metric='euclidean', segments=0, tile=0, g_window=0):
     """Row-form re-ranking straight from the features (ops.re_ranking_from_features:
     no [N, N] matrix, any gallery size) -> [Q, G]; NumPy in -> NumPy out, CUDA
-    tensors in -> tensor out."""
+    tensors in -> tensor out.  gallery_feats may be an ops.RerankGallery
+    prepared once (its metric; k1 at most its k1): the same bits per batch."""
     as_numpy = not isinstance(query_feats, torch.Tensor)
+    if isinstance(gallery_feats, ops.RerankGallery):
+        if metric != gallery_feats.metric:
+            raise RuntimeError('re_ranking_from_features: metric %r, the RerankGallery was '
+                               'prepared with %r' % (metric, gallery_feats.metric))
+        out = gallery_feats.re_rank(_to_dev(query_feats).contiguous(), k1, k2, lambda_value,
+                                    segments=segments, tile=tile, g_window=g_window)
+        return out.cpu().numpy() if as_numpy else out
     q, g = _to_dev(query_feats), _to_dev(gallery_feats)
     out = ops.re_ranking_from_features(torch.cat([q, g]), q.shape[0], k1, k2, lambda_value,
                                        metric=metric, segments=segments, tile=tile,
