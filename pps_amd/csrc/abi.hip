@@ -468,14 +468,10 @@ int pps_re_ranking_ld(const float* q_g, int64_t ld_qg, const float* q_q, int64_t
   PPS_ENFORCE(Q > 0 && G > 0, "bad shape");
   PPS_ENFORCE(ld_qg >= G && ld_qq >= Q && ld_gg >= G, "leading dims smaller than the rows");
   PPS_ENFORCE(k1 >= 1 && k1 + 1 <= 64, "k1 + 1 must be <= 64");
-  PPS_ENFORCE(k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
-  const int K1 = k1 + 1, Kh = (int)lrint(k1 / 2.0) + 1;
-  PPS_ENFORCE(K1 + K1 * Kh <= 1024, "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
-  PPS_ENFORCE(k2 * (K1 + K1 * Kh <= 256 ? 256 : (K1 + K1 * Kh <= 512 ? 512 : 1024)) <= 4096,
-              "k2 * V row capacity must be <= 4096");
+  PPS_TRY(rr_layout_guard(__func__, k1, k2));
   PPS_ENFORCE(jaccard_lds_bytes(G) + 2048 <= kLdsBytesGfx950,
               "G must be <= 38400 (the Jaccard pass keeps a gallery row in LDS)");
-  PPS_ENFORCE((Q + G) >= K1, "need Q + G >= k1 + 1");
+  PPS_ENFORCE((Q + G) >= k1 + 1, "need Q + G >= k1 + 1");
   PPS_ENFORCE((flags & ~(PPS_RERANK_SYMMETRIC | PPS_RERANK_WHOLE)) == 0,
               "unknown re-ranking flags");
   PPS_ENFORCE(!(flags & PPS_RERANK_WHOLE) ||
@@ -509,20 +505,16 @@ static int rerank_rows_guards(const char* fn, int64_t Q, int64_t G, int k1, int 
   PPS_ENFORCE_AS(fn, Q + G < (1ll << 31), "N = Q + G must fit int32");
   PPS_ENFORCE_AS(fn, k1 >= 1 && k1 + 1 <= 64 && k1 + 1 <= kTkwMaxK,
                  "k1 + 1 must be <= 64 and <= pps_search_max_k()");
-  PPS_ENFORCE_AS(fn, k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
-  const int K1 = k1 + 1, Kh = (int)lrint(k1 / 2.0) + 1;
-  PPS_ENFORCE_AS(fn, K1 + K1 * Kh <= 1024,
-                 "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
-  const int vcap = K1 + K1 * Kh <= 256 ? 256 : (K1 + K1 * Kh <= 512 ? 512 : 1024);
-  PPS_ENFORCE_AS(fn, k2 * vcap <= 4096, "k2 * V row capacity must be <= 4096");
-  PPS_ENFORCE_AS(fn, (Q + G) >= K1, "need Q + G >= k1 + 1");
+  PPS_TRY(rr_layout_guard(fn, k1, k2));
+  const int qcap = RrLayout(k1, k2).qcap;
+  PPS_ENFORCE_AS(fn, (Q + G) >= k1 + 1, "need Q + G >= k1 + 1");
   PPS_ENFORCE_AS(fn, g_window >= 0 && g_window <= kJacMaxWindow,
                  "g_window must be in [0, " + std::to_string(kJacMaxWindow) + "] (0 = auto)");
   PPS_ENFORCE_AS(fn, g_window == 0 || (G + g_window - 1) / g_window <= 65535,
                  "more than 65535 gallery windows");
-  if ((Q + G) * (int64_t)(k2 * vcap) >= (1ll << 31)) {
+  if ((Q + G) * (int64_t)qcap >= (1ll << 31)) {
     set_error(std::string(fn) + ": N * qcap = " + std::to_string(Q + G) + " * " +
-              std::to_string(k2 * vcap) + " entries of the inverted index do not fit int32");
+              std::to_string(qcap) + " entries of the inverted index do not fit int32");
     return PPS_ERR_CAPACITY;
   }
   return PPS_OK;
@@ -559,16 +551,16 @@ int pps_re_ranking_features(const uint16_t* x2t, const float* xsq, const float* 
                             int64_t G, int D, int metric, int k1, int k2, double lambda_value,
                             int segments, int tile, int64_t g_window, void* workspace,
                             int64_t ws_bytes, float* out, void* stream) {
+  // the operands: x = [queries; gallery] (N rows) and the gallery rows' own planes
+  RrRows src{};
+  src.x = h2_operand(x2t, xsq, xrs, Q + G);
+  src.g = h2_operand(g2t, gsq, grs, G);
+  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
   PPS_ENFORCE(workspace && out, "null pointer");
   PPS_TRY(rerank_rows_guards(__func__, Q, G, k1, k2, g_window));   // Q, G > 0, N in int32
-  // the operands: x = [queries; gallery] (N rows) and the gallery rows' own planes
-  PPS_TRY(h2_operands_guard(__func__, x2t, Q + G, xsq, xrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, src.x, src.g, D, metric));
   PPS_TRY(fused_plan_guard(__func__, segments, tile));
   PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  RrRows src{};
-  src.x2t = x2t; src.xsq = xsq; src.xrs = xrs;
-  src.g2t = g2t; src.gsq = gsq; src.grs = grs;
-  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
   return rerank_rows(src, Q, G, k1, k2, lambda_value, g_window, workspace,
                      ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
 }
@@ -587,17 +579,17 @@ int pps_re_ranking_prepared(const uint16_t* q2t, const float* qsq, const float* 
                             int k2, double lambda_value, int segments, int tile,
                             int64_t g_window, void* workspace, int64_t ws_bytes, float* out,
                             void* stream) {
+  RrPrepared src{};
+  src.q = h2_operand(q2t, qsq, qrs, Q);
+  src.g = h2_operand(g2t, gsq, grs, G);
+  src.nn_vals = nn_vals; src.nn_idx = nn_idx; src.nn_ld = nn_ld; src.g_rowmax = g_rowmax;
+  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
   PPS_ENFORCE(workspace && out && nn_vals && nn_idx && g_rowmax, "null pointer");
   PPS_TRY(rerank_rows_guards(__func__, Q, G, k1, k2, g_window));   // Q, G > 0, N in int32
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, src.q, src.g, D, metric));
   PPS_TRY(fused_plan_guard(__func__, segments, tile));
   PPS_ENFORCE(nn_ld >= k1 + 1, "nn_ld must be >= k1 + 1");
   PPS_ENFORCE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  RrPrepared src{};
-  src.q2t = q2t; src.qsq = qsq; src.qrs = qrs;
-  src.g2t = g2t; src.gsq = gsq; src.grs = grs;
-  src.nn_vals = nn_vals; src.nn_idx = nn_idx; src.nn_ld = nn_ld; src.g_rowmax = g_rowmax;
-  src.D = D; src.metric = metric; src.segments = segments; src.tile = tile;
   return rerank_prepared(src, Q, G, k1, k2, lambda_value, g_window, workspace,
                          ws_bytes < 0 ? 0 : (size_t)ws_bytes, out, as_stream(stream));
 }

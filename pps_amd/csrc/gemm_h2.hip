@@ -362,15 +362,15 @@ int pps_split_f16x2_sqnorm_tiled(const float* x, int64_t rows, int D, int64_t ld
 int pps_distmat_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
                          const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
                          int D, int metric, float* out, int64_t ldo, int tile, void* stream) {
+  const H2Operand q = h2_operand(q2t, qsq, qrs, Q), g = h2_operand(g2t, gsq, grs, G);
   // empty operands included: the pointers and their alignment are checked for every shape
-  PPS_ENFORCE(q2t && qsq && qrs && g2t && gsq && grs && out, "null pointer");
+  PPS_ENFORCE(q.complete() && g.complete() && out, "null pointer");
   PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q, g, D, metric));
   PPS_ENFORCE(ldo >= G, "ldo < G");
   PPS_ENFORCE(tile >= 0 && tile < kH2NumTiles, "h2 tile must be 0.." + std::to_string(kH2NumTiles - 1));
   if (Q == 0 || G == 0) return PPS_OK;
-  const GemmParams p = h2_params(q2t, Q, Q, qsq, qrs, g2t, G, gsq, grs, D, metric, out, ldo);
-  return launch_gemm_h2(p, as_stream(stream), tile);
+  return launch_gemm_h2(h2_params(q, g, D, metric, out, ldo), as_stream(stream), tile);
 }
 
 int pps_distmat_h2_self_tiled(const uint16_t* x2t, int64_t N, const float* xsq, const float* xrs,
@@ -385,6 +385,6 @@ int pps_distmat_h2_self_tiled(const uint16_t* x2t, int64_t N, const float* xsq, 
   PPS_ENFORCE(h2_planes_bytes(N, D) < kMaxBufBytes, "planes over 2 GiB");
   PPS_ENFORCE(N * ldo < (1ll << 31), "output larger than 2^31 elements");
   if (N == 0) return PPS_OK;
-  const GemmParams p = h2_params(x2t, N, N, xsq, xrs, x2t, N, xsq, xrs, D, metric, out, ldo, 1);
-  return launch_gemm_h2(p, as_stream(stream), tile);
+  const H2Operand x = h2_operand(x2t, xsq, xrs, N);
+  return launch_gemm_h2(h2_params(x, x, D, metric, out, ldo, 1), as_stream(stream), tile);
 }

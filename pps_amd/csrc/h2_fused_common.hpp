@@ -137,17 +137,15 @@ struct PairOperands {
   int64_t Q;
   int nkc, metric;
 };
-// the first Q rows of a planes holding Qrows rows; b planes of G rows
-inline PairOperands pair_operands(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq,
-                                  const float* qrs, const uint16_t* g2t, const float* gsq,
-                                  const float* grs, int64_t G, int D, int metric) {
+// the rows of q (a-rows) against the planes of g
+inline PairOperands pair_operands(const H2Operand& q, const H2Operand& g, int D, int metric) {
   PairOperands o{};
-  o.q2t = reinterpret_cast<const unsigned char*>(q2t);
-  o.g2t = reinterpret_cast<const unsigned char*>(g2t);
-  o.q_plane = h2_plane_elems(Qrows, D) * 2;
-  o.g_plane = h2_plane_elems(G, D) * 2;
-  o.qsq = qsq; o.qrs = qrs; o.gsq = gsq; o.grs = grs;
-  o.Q = Q;
+  o.q2t = reinterpret_cast<const unsigned char*>(q.planes);
+  o.g2t = reinterpret_cast<const unsigned char*>(g.planes);
+  o.q_plane = h2_plane_elems(q.plane_rows, D) * 2;
+  o.g_plane = h2_plane_elems(g.plane_rows, D) * 2;
+  o.qsq = q.sq; o.qrs = q.rs; o.gsq = g.sq; o.grs = g.rs;
+  o.Q = q.rows;
   o.nkc = D / 32;
   o.metric = metric;
   return o;

@@ -108,14 +108,12 @@ pair_dist_h2_kernel(PairOperands o, PairDistArgs a) {
   }
 }
 
-int pair_dist_h2(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq, const float* qrs,
-                 const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
-                 int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
-                 hipStream_t st) {
-  if (Q == 0 || G == 0 || cap == 0) return PPS_OK;
-  const PairOperands o = pair_operands(q2t, Q, Qrows, qsq, qrs, g2t, gsq, grs, G, D, metric);
-  const PairDistArgs a{(int)G, cap, lists, counts, out};
-  const unsigned grid = (unsigned)((Q + kPairWaves - 1) / kPairWaves);
+int pair_dist_h2(const H2Operand& q, const H2Operand& g, int D, int metric, const int32_t* lists,
+                 const int32_t* counts, int cap, float* out, hipStream_t st) {
+  if (q.rows == 0 || g.rows == 0 || cap == 0) return PPS_OK;
+  const PairOperands o = pair_operands(q, g, D, metric);
+  const PairDistArgs a{(int)g.rows, cap, lists, counts, out};
+  const unsigned grid = (unsigned)((q.rows + kPairWaves - 1) / kPairWaves);
   hipLaunchKernelGGL(pair_dist_h2_kernel, dim3(grid), dim3(64 * kPairWaves), 0, st, o, a);
   PPS_CHECK_LAUNCH("pair_dist_h2_kernel");
   return PPS_OK;
@@ -153,33 +151,29 @@ pair_dist_h2_parts_kernel(PairOperands o, PairPart p, PairDistArgs a) {
   }
 }
 
-int pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq,
-                       const float* qrs, const uint16_t* b0_2t, const float* b0sq,
-                       const float* b0rs, int64_t B0, const uint16_t* b1_2t, const float* b1sq,
-                       const float* b1rs, int64_t B1, int D, int metric, const int32_t* lists,
-                       const int32_t* counts, int cap, float* out, hipStream_t st) {
-  if (Q == 0 || B0 + B1 == 0 || cap == 0) return PPS_OK;
+int pair_dist_h2_parts(const H2Operand& q, const H2Operand& b0, const H2Operand& b1, int D,
+                       int metric, const int32_t* lists, const int32_t* counts, int cap,
+                       float* out, hipStream_t st) {
+  if (q.rows == 0 || b0.rows + b1.rows == 0 || cap == 0) return PPS_OK;
   // an empty part is never addressed: the clamp keeps every index in the other
-  const PairOperands o = pair_operands(q2t, Q, Qrows, qsq, qrs, b0_2t, b0sq, b0rs, B0, D, metric);
+  const PairOperands o = pair_operands(q, b0, D, metric);
   PairPart p{};
-  p.g2t = reinterpret_cast<const unsigned char*>(b1_2t);
-  p.g_plane = h2_plane_elems(B1, D) * 2;
-  p.gsq = b1sq; p.grs = b1rs;
-  p.B0 = (int)B0;
-  const PairDistArgs a{(int)(B0 + B1), cap, lists, counts, out};
-  const unsigned grid = (unsigned)((Q + kPairWaves - 1) / kPairWaves);
+  p.g2t = reinterpret_cast<const unsigned char*>(b1.planes);
+  p.g_plane = h2_plane_elems(b1.plane_rows, D) * 2;
+  p.gsq = b1.sq; p.grs = b1.rs;
+  p.B0 = (int)b0.rows;
+  const PairDistArgs a{(int)(b0.rows + b1.rows), cap, lists, counts, out};
+  const unsigned grid = (unsigned)((q.rows + kPairWaves - 1) / kPairWaves);
   hipLaunchKernelGGL(pair_dist_h2_parts_kernel, dim3(grid), dim3(64 * kPairWaves), 0, st, o, p, a);
   PPS_CHECK_LAUNCH("pair_dist_h2_parts_kernel");
   return PPS_OK;
 }
 
 // pps_distmat_h2_tiled's launch with the a planes' own plane stride
-int distmat_h2_head(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
-                    const float* ars, const uint16_t* b2t, const float* bsq, const float* brs,
-                    int64_t N, int D, int metric, float* out, int64_t ldo, hipStream_t st) {
-  if (M == 0 || N == 0) return PPS_OK;
-  return launch_gemm_h2(h2_params(a2t, M, Arows, asq, ars, b2t, N, bsq, brs, D, metric, out, ldo),
-                        st, 0);
+int distmat_h2_head(const H2Operand& a, const H2Operand& b, int D, int metric, float* out,
+                    int64_t ldo, hipStream_t st) {
+  if (a.rows == 0 || b.rows == 0) return PPS_OK;
+  return launch_gemm_h2(h2_params(a, b, D, metric, out, ldo), st, 0);
 }
 
 }  // namespace pps
@@ -194,17 +188,18 @@ int pps_collect_matches_h2(const uint16_t* q2t, int64_t Q, const float* qsq, con
                            int64_t g_offset, int Pmax, float* pos_d, int32_t* pos_idx,
                            int32_t* pos_cnt, int Jmax, float* junk_d, int32_t* junk_idx,
                            int32_t* junk_cnt, void* stream) {
+  const H2Operand q = h2_operand(q2t, qsq, qrs, Q), g = h2_operand(g2t, gsq, grs, G);
   PPS_ENFORCE(qcam && gcam && members && q_beg && q_end && pos_d && pos_idx && pos_cnt &&
                   junk_d && junk_idx && junk_cnt,
               "null pointer");
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q, g, D, metric));
   PPS_ENFORCE(Pmax > 0 && Jmax > 0, "bad shape");
   PPS_ENFORCE(g_offset >= 0 && g_offset + G < (1ll << 31), "gallery indices must fit int32");
   if (Q == 0) return PPS_OK;
   // an empty gallery still writes every query's zero counts
-  PPS_ENFORCE(q2t && qsq && qrs, "null pointer");
+  PPS_ENFORCE(q.complete(), "null pointer");
   PPS_ENFORCE(aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
-  const PairOperands o = pair_operands(q2t, Q, Q, qsq, qrs, g2t, gsq, grs, G, D, metric);
+  const PairOperands o = pair_operands(q, g, D, metric);
   const MatchArgs a{qcam, gcam, members, q_beg, q_end, g_offset, Pmax, Jmax, pos_d, pos_idx,
                     pos_cnt, junk_d, junk_idx, junk_cnt};
   const unsigned grid = (unsigned)((Q + kPairWaves - 1) / kPairWaves);
@@ -218,14 +213,14 @@ int pps_pair_dist_h2(const uint16_t* q2t, int64_t Q, const float* qsq, const flo
                      const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
                      int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
                      void* stream) {
+  const H2Operand q = h2_operand(q2t, qsq, qrs, Q), g = h2_operand(g2t, gsq, grs, G);
   PPS_ENFORCE(lists && out, "null pointer");
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q, g, D, metric));
   PPS_ENFORCE(G < (1ll << 31), "Q and G must fit int32");
   PPS_ENFORCE(cap >= 1, "cap must be >= 1");
   if (Q == 0) return PPS_OK;
   PPS_ENFORCE(G > 0, "a listed pair needs a b-row (G > 0)");
-  return pair_dist_h2(q2t, Q, Q, qsq, qrs, g2t, gsq, grs, G, D, metric, lists, counts, cap, out,
-                      as_stream(stream));
+  return pair_dist_h2(q, g, D, metric, lists, counts, cap, out, as_stream(stream));
 }
 
 int pps_pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
@@ -233,13 +228,14 @@ int pps_pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, const float* qsq, con
                            const uint16_t* b1_2t, const float* b1sq, const float* b1rs, int64_t B1,
                            int D, int metric, const int32_t* lists, const int32_t* counts, int cap,
                            float* out, void* stream) {
+  const H2Operand q = h2_operand(q2t, qsq, qrs, Q);
+  const H2Operand b0 = h2_operand(b0_2t, b0sq, b0rs, B0), b1 = h2_operand(b1_2t, b1sq, b1rs, B1);
   PPS_ENFORCE(lists && out, "null pointer");
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, b0_2t, b0sq, b0rs, B0, D, metric));
-  PPS_TRY(h2_operands_guard(__func__, q2t, Q, qsq, qrs, b1_2t, b1sq, b1rs, B1, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q, b0, D, metric));
+  PPS_TRY(h2_operands_guard(__func__, q, b1, D, metric));
   PPS_ENFORCE(B0 + B1 < (1ll << 31), "B0 + B1 must fit int32");
   PPS_ENFORCE(cap >= 1, "cap must be >= 1");
   if (Q == 0) return PPS_OK;
   PPS_ENFORCE(B0 > 0 && B1 > 0, "a listed pair needs a b-row in each part (B0, B1 > 0)");
-  return pair_dist_h2_parts(q2t, Q, Q, qsq, qrs, b0_2t, b0sq, b0rs, B0, b1_2t, b1sq, b1rs, B1, D,
-                            metric, lists, counts, cap, out, as_stream(stream));
+  return pair_dist_h2_parts(q, b0, b1, D, metric, lists, counts, cap, out, as_stream(stream));
 }

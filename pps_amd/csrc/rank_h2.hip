@@ -342,8 +342,7 @@ static int launch_rank_count_tile(int tile, const GemmParams& p, const RankH2Arg
 // What the two count entries take alike (pps_abi.h), their shared guards and,
 // once those passed, the kernel's arguments.
 struct CountCall {
-  const uint16_t* q2t; int64_t Q; const float* qsq; const float* qrs;
-  const uint16_t* g2t; const float* gsq; const float* grs; int64_t G;
+  H2Operand q, g;
   int D, metric;
   int64_t g_offset;
   int Ptot;
@@ -351,19 +350,11 @@ struct CountCall {
   int segments, tile;
   int32_t* hist;
 };
-// filled by name from an entry's own parameters (both entries name them alike)
-#define PPS_COUNT_CALL(c)                                                                  \
-  CountCall c{};                                                                           \
-  c.q2t = q2t; c.Q = Q; c.qsq = qsq; c.qrs = qrs; c.g2t = g2t; c.gsq = gsq; c.grs = grs;   \
-  c.G = G; c.D = D; c.metric = metric; c.g_offset = g_offset; c.Ptot = Ptot;               \
-  c.sorted_d = sorted_d; c.sorted_idx = sorted_idx; c.pos_total = pos_total;               \
-  c.segments = segments; c.tile = tile; c.hist = hist
 static int rank_count_guards(const char* fn, const CountCall& c) {
   PPS_ENFORCE_AS(fn, c.sorted_d && c.sorted_idx && c.pos_total && c.hist, "null pointer");
-  PPS_TRY(h2_operands_guard(fn, c.q2t, c.Q, c.qsq, c.qrs, c.g2t, c.gsq, c.grs, c.G, c.D,
-                            c.metric));
+  PPS_TRY(h2_operands_guard(fn, c.q, c.g, c.D, c.metric));
   const int Ptot = c.Ptot;
-  const int64_t g_offset = c.g_offset, G = c.G;
+  const int64_t g_offset = c.g_offset, G = c.g.rows;
   PPS_ENFORCE_AS(fn, Ptot > 0, "bad shape");
   PPS_ENFORCE_AS(fn, g_offset >= 0 && g_offset + G < (1ll << 31),
                  "gallery indices must fit int32");
@@ -379,12 +370,13 @@ static int rank_count_guards(const char* fn, const CountCall& c) {
 static void rank_count_plan(const CountCall& c, GemmParams& p, RankH2Args& a) {
   int BM, BN;
   search_tile_shape(c.tile, BM, BN);
-  a.plan = fused_plan(c.Q, c.G, fused_segments(c.Q, c.G, c.segments, BM, BN), BM, BN);
+  const int64_t Q = c.q.rows, G = c.g.rows;
+  a.plan = fused_plan(Q, G, fused_segments(Q, G, c.segments, BM, BN), BM, BN);
   a.g_offset = c.g_offset;
   a.Ptot = c.Ptot;
   a.sorted_d = c.sorted_d; a.sorted_idx = c.sorted_idx; a.pos_total = c.pos_total;
   a.hist = c.hist;
-  p = h2_params(c.q2t, c.Q, c.Q, c.qsq, c.qrs, c.g2t, c.G, c.gsq, c.grs, c.D, c.metric);
+  p = h2_params(c.q, c.g, c.D, c.metric);
 }
 
 }  // namespace pps
@@ -408,7 +400,8 @@ int pps_rank_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, co
                             const int32_t* junk_idx, const int32_t* junk_cnt, int segments,
                             int tile, void*, int64_t, int32_t* hist, int32_t* before,
                             void* stream) {
-  PPS_COUNT_CALL(c);
+  const CountCall c{h2_operand(q2t, qsq, qrs, Q), h2_operand(g2t, gsq, grs, G), D, metric,
+                    g_offset, Ptot, sorted_d, sorted_idx, pos_total, segments, tile, hist};
   PPS_ENFORCE(junk_d && junk_idx && junk_cnt && before, "null pointer");
   PPS_ENFORCE(Jmax > 0, "bad shape");
   PPS_TRY(rank_count_guards(__func__, c));
@@ -435,7 +428,8 @@ int pps_cmc_count_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, con
                            int Jmax, const float* junk_d, const int32_t* junk_idx,
                            const int32_t* junk_cnt, int segments, int tile, void*, int64_t,
                            int32_t* hist, void* stream) {
-  PPS_COUNT_CALL(c);
+  const CountCall c{h2_operand(q2t, qsq, qrs, Q), h2_operand(g2t, gsq, grs, G), D, metric,
+                    g_offset, Ptot, sorted_d, sorted_idx, pos_total, segments, tile, hist};
   PPS_ENFORCE((qcam == nullptr) == (gcam == nullptr),
               "qcam and gcam are given together (separate_camera_set) or not at all");
   PPS_ENFORCE(gcam || (junk_d && junk_idx && junk_cnt && Jmax > 0),

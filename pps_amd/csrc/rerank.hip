@@ -864,51 +864,15 @@ rerank_jaccard_kernel(int64_t Q, int64_t N, const float* __restrict__ od, int64_
   }
 }
 
-namespace {
-struct RrLayout {  // V-row capacities of a (k1, k2) configuration
-  int K1, Kh, vcap, qcap;
-  RrLayout(int k1, int k2) {
-    K1 = k1 + 1;
-    Kh = (int)lrint(k1 / 2.0) + 1;  // int(np.around(k1 / 2.)) + 1
-    const int vbound = K1 + K1 * Kh;
-    vcap = vbound <= 256 ? 256 : (vbound <= 512 ? 512 : 1024);
-    qcap = k2 * vcap;
-  }
-};
-}  // namespace
-
 // The N x N OD region of a call: the dense normalised distance, or in place
 // (symmetric, N >= 16384, 16-byte block rows) only q_g^T ([G][Q rounded up to
 // 4]; none with PPS_RERANK_WHOLE, where it is M's lower-left block) plus the
-// squared top-k's scratch.  The OD region is the workspace's first carve, so
-// its base is the workspace's (256-B aligned) and decides nothing here.
-static bool rr_inplace(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq,
-                       const float* gg, int64_t ldgg, int64_t Q, int64_t G, int K1, int flags,
-                       float* od) {
-  const bool whole = (flags & PPS_RERANK_WHOLE) != 0;
-  const RrMatrix M{qg, qq, gg, whole ? qq + Q * ldqq : od, ldqg, ldqq, ldgg,
-                   whole ? ldqq : (Q + 3) / 4 * 4, Q, G, nullptr};
-  return (flags & PPS_RERANK_SYMMETRIC) && topk_rr_eligible(M, K1) &&
-         getenv_flag_off("PPS_RERANK_INPLACE") == false;
-}
-
+// squared top-k's scratch.
 static size_t rr_od_bytes(bool inplace, bool whole, int64_t Q, int64_t G, int K1) {
   const int64_t N = Q + G;
   if (!inplace) return sizeof(float) * (size_t)(N * od_stride(N));
   const size_t tb = whole ? 0 : (sizeof(float) * (size_t)(G * ((Q + 3) / 4 * 4)) + 255) / 256 * 256;
   return tb + topk_rr_sq_scratch_bytes(N, K1);
-}
-
-// Everything past the OD region
-static size_t rr_rest_bytes(int64_t Q, int64_t G, int k1, int k2) {
-  const int64_t N = Q + G;
-  const RrLayout L(k1, k2);
-  const int64_t K1 = L.K1, vcap = L.vcap, qcap = L.qcap;
-  auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t s = r(4 * N) + r(4 * N * K1) * 2 + r(4 * N * vcap) * 2 + r(4 * N);
-  s += r(4 * N * qcap) * 2 + r(4 * N) + r(4 * (N + 1)) * 3 + r(4 * N * qcap) * 2;
-  s += r(4 * N) + r(4);   // V_qe overflow rows + count
-  return s;
 }
 
 // The sparse per-row structures of a call (workspace carves)
@@ -920,6 +884,86 @@ struct RrSparse {
   int32_t* csc_row; float* csc_val;
   int32_t* ovf_rows; int32_t* ovf_n;
 };
+
+// The workspace of every re-ranking form, the one statement of its layout:
+// byte offsets of the regions in this order, each rounded up to 256 bytes --
+//   head     the form's own first region: OD (dense), q_g^T plus the squared
+//            top-k's scratch (in place), or nothing (row forms)
+//   rowmax   [N] the maxima OD divides by (the dense form's colmax)
+//   topv, rank                [N][K1] each: the neighbours' values and indices
+//   v_idx, v_val, v_cnt       [N][vcap] twice, [N]: the V rows
+//   q_idx, q_val, q_cnt       [N][qcap] twice, [N]: the V_qe rows
+//   col_cnt, start, fill      [N + 1] each: the inverted index's columns
+//   csc_row, csc_val          [N][qcap] each: its entries
+//   ovf_rows, ovf_n           [N], [1]: V_qe rows left to the block kernel
+//   tail     the fused search's workspace (features path), or nothing
+// and `total`, which every size function returns and every call checks.  A
+// form that needs more (rerank_prepared) appends its regions at `total`.
+struct RrCarve {
+  size_t head, rowmax, topv, rank, v_idx, v_val, v_cnt, q_idx, q_val, q_cnt, col_cnt, start, fill,
+      csc_row, csc_val, ovf_rows, ovf_n, tail, total;
+  size_t head_bytes, tail_bytes;   // as asked for (not rounded)
+  static size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+  RrCarve(int64_t N, const RrLayout& L, size_t head_bytes_, size_t tail_bytes_)
+      : head_bytes(head_bytes_), tail_bytes(tail_bytes_) {
+    const size_t K1 = L.K1, vcap = L.vcap, qcap = L.qcap;
+    size_t p = 0;
+    auto take = [&](size_t bytes) {
+      const size_t r = p;
+      p += round256(bytes);
+      return r;
+    };
+    head = take(head_bytes);
+    rowmax = take(4 * N);
+    topv = take(4 * N * K1);
+    rank = take(4 * N * K1);
+    v_idx = take(4 * N * vcap);
+    v_val = take(4 * N * vcap);
+    v_cnt = take(4 * N);
+    q_idx = take(4 * N * qcap);
+    q_val = take(4 * N * qcap);
+    q_cnt = take(4 * N);
+    col_cnt = take(4 * (N + 1));
+    start = take(4 * (N + 1));
+    fill = take(4 * (N + 1));
+    csc_row = take(4 * N * qcap);
+    csc_val = take(4 * N * qcap);
+    ovf_rows = take(4 * N);
+    ovf_n = take(4);
+    tail = take(tail_bytes);
+    total = p;
+  }
+  // the regions of a workspace at ws
+  struct Bound {
+    RrSparse sp;
+    float* rowmax;
+    float* topv;
+  };
+  Bound bind(void* ws) const {
+    char* base = reinterpret_cast<char*>(ws);
+    auto f32 = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
+    return {{i32(rank), i32(v_idx), f32(v_val), i32(v_cnt), i32(q_idx), f32(q_val), i32(q_cnt),
+             i32(col_cnt), i32(start), i32(fill), i32(csc_row), f32(csc_val), i32(ovf_rows),
+             i32(ovf_n)},
+            f32(rowmax), f32(topv)};
+  }
+};
+
+// The dense entry's carve: its head is the OD region of the path the call
+// takes (inplace: which).  The OD region is the first, so its base is the
+// workspace's: ws, or in a size function any 256-byte aligned pointer (the
+// base decides through its alignment only).
+static RrCarve rr_dense_carve(const RrIn& in, int64_t Q, int64_t G, const RrLayout& L, int flags,
+                              void* ws, bool& inplace) {
+  const bool whole = (flags & PPS_RERANK_WHOLE) != 0;
+  const RrMatrix M{in.qg, in.qq, in.gg,
+                   whole ? in.qq + Q * in.ldqq : reinterpret_cast<const float*>(ws),
+                   in.ldqg, in.ldqq, in.ldgg, whole ? in.ldqq : (Q + 3) / 4 * 4, Q, G, nullptr};
+  inplace = (flags & PPS_RERANK_SYMMETRIC) && topk_rr_eligible(M, L.K1) &&
+            getenv_flag_off("PPS_RERANK_INPLACE") == false;
+  return RrCarve(Q + G, L, rr_od_bytes(inplace, whole, Q, G, L.K1), 0);
+}
 
 // Stages 4 and 5 (V_qe and its inverted index) from the finished V rows
 static int rr_vqe_csc(int64_t N, const RrLayout& L, int k2, const RrSparse& sp, hipStream_t st) {
@@ -970,39 +1014,19 @@ int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const f
   const int K1 = L.K1, Kh = L.Kh, vcap = L.vcap, qcap = L.qcap;
   const int64_t ldT = (Q + 3) / 4 * 4;
   const bool whole = (flags & PPS_RERANK_WHOLE) != 0;
-  const bool inplace = rr_inplace(qg, ldqg, qq, ldqq, gg, ldgg, Q, G, K1, flags,
-                                  reinterpret_cast<float*>(ws));
-  const size_t odb = rr_od_bytes(inplace, whole, Q, G, K1);
-  // workspace carve-up (all 256-B aligned)
-  char* p = reinterpret_cast<char*>(ws);
-  auto take = [&](size_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  float* od = reinterpret_cast<float*>(take(odb));
-  float* colmax = reinterpret_cast<float*>(take(sizeof(float) * N));
-  float* topv = reinterpret_cast<float*>(take(sizeof(float) * N * K1));
-  int32_t* rank = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N * K1));
-  int32_t* v_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N * vcap));
-  float* v_val = reinterpret_cast<float*>(take(sizeof(float) * N * vcap));
-  int32_t* v_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
-  int32_t* q_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N * qcap));
-  float* q_val = reinterpret_cast<float*>(take(sizeof(float) * N * qcap));
-  int32_t* q_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
-  int32_t* col_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (N + 1)));
-  int32_t* start = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (N + 1)));
-  int32_t* fill = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (N + 1)));
-  int32_t* csc_row = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N * qcap));
-  float* csc_val = reinterpret_cast<float*>(take(sizeof(float) * N * qcap));
-  int32_t* ovf_rows = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
-  int32_t* ovf_n = reinterpret_cast<int32_t*>(take(sizeof(int32_t)));
-  if ((size_t)(p - reinterpret_cast<char*>(ws)) > ws_bytes) {
-    set_error("rerank workspace too small: need " +
-              std::to_string((size_t)(p - reinterpret_cast<char*>(ws))) + " bytes");
+  const RrIn in{qg, qq, gg, ldqg, ldqq, ldgg};
+  bool inplace;
+  const RrCarve carve = rr_dense_carve(in, Q, G, L, flags, ws, inplace);
+  if (carve.total > ws_bytes) {
+    set_error("rerank workspace too small: need " + std::to_string(carve.total) + " bytes");
     return PPS_ERR_CAPACITY;
   }
-  const RrIn in{qg, qq, gg, ldqg, ldqq, ldgg};
+  const size_t odb = carve.head_bytes;
+  float* od = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + carve.head);
+  const RrCarve::Bound bound = carve.bind(ws);
+  const RrSparse& sp = bound.sp;
+  float* colmax = bound.rowmax;
+  float* topv = bound.topv;
   // In place (symmetric M, long rows, 16-byte rows): no N x N OD buffer --
   // its top-k, the V weights and the Jaccard blend read M's blocks and
   // compute (m * m) / colmax on the fly; q_g^T (the block that is nobody's
@@ -1038,7 +1062,7 @@ int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const f
     // scratch for the squared top-k: the OD region past q_g^T
     const size_t tb = whole ? 0 : (sizeof(float) * (size_t)(G * ldT) + 255) / 256 * 256;
     const int rc = topk_rr_sq(M, K1, colmax, reinterpret_cast<char*>(od) + tb, odb - tb, topv,
-                              rank, st);
+                              sp.rank, st);
     if (rc != PPS_OK) return rc;
   } else {
     if (flags & PPS_RERANK_SYMMETRIC) {
@@ -1057,13 +1081,13 @@ int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const f
                          dim3(256), 0, st, in, Q, G, colmax, od, ldo, (int64_t)0, N);
     }
     PPS_CHECK_LAUNCH_S("rerank_build_od_kernel", st);
-    const int rc = topk(od, N, N, ldo, K1, topv, rank, st);
+    const int rc = topk(od, N, N, ldo, K1, topv, sp.rank, st);
     if (rc != PPS_OK) return rc;
   }
   PPS_CHECK_LAUNCH_S("rerank topk", st);
   if (debug_sync()) {  // every neighbour index must address a row of OD
     std::vector<int32_t> h((size_t)(N * K1));
-    (void)hipMemcpy(h.data(), rank, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(h.data(), sp.rank, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
     for (size_t t = 0; t < h.size(); ++t)
       if (h[t] < 0 || h[t] >= N) {
         set_error("rerank topk: rank[" + std::to_string(t / K1) + "][" +
@@ -1074,87 +1098,53 @@ int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const f
   const VRowsLds vl(K1, Kh);
   if (inplace)
     hipLaunchKernelGGL(rerank_v_rows_kernel<kVOtf>, dim3((unsigned)N), dim3(64), vl.bytes(), st, od,
-                       N, ldo, rank, K1, Kh, vcap, vl.E2, v_idx, v_val, v_cnt, M);
+                       N, ldo, sp.rank, K1, Kh, vcap, vl.E2, sp.v_idx, sp.v_val, sp.v_cnt, M);
   else
     hipLaunchKernelGGL(rerank_v_rows_kernel<kVDense>, dim3((unsigned)N), dim3(64), vl.bytes(), st,
-                       od, N, ldo, rank, K1, Kh, vcap, vl.E2, v_idx, v_val, v_cnt, M);
+                       od, N, ldo, sp.rank, K1, Kh, vcap, vl.E2, sp.v_idx, sp.v_val, sp.v_cnt, M);
   PPS_CHECK_LAUNCH_S("rerank_v_rows_kernel", st);
   const int qc = k2 != 1 ? qcap : vcap;
-  const RrSparse sp{rank, v_idx, v_val, v_cnt, q_idx, q_val, q_cnt, col_cnt, start, fill,
-                    csc_row, csc_val, ovf_rows, ovf_n};
   const int src = rr_vqe_csc(N, L, k2, sp, st);
   if (src != PPS_OK) return src;
   const size_t jac_lds = jaccard_lds_bytes(G);
   if (inplace)
     hipLaunchKernelGGL(rerank_jaccard_kernel<kJacOtf>, dim3((unsigned)Q), dim3(kJacThreads),
-                       jac_lds, st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row,
-                       csc_val, lam, one_m_lam, out, G);
+                       jac_lds, st, Q, N, od, ldo, M, sp.q_idx, sp.q_val, sp.q_cnt, qc, sp.start,
+                       sp.csc_row, sp.csc_val, lam, one_m_lam, out, G);
   else
     hipLaunchKernelGGL(rerank_jaccard_kernel<kJacDense>, dim3((unsigned)Q), dim3(kJacThreads),
-                       jac_lds, st, Q, N, od, ldo, M, q_idx, q_val, q_cnt, qc, start, csc_row,
-                       csc_val, lam, one_m_lam, out, G);
+                       jac_lds, st, Q, N, od, ldo, M, sp.q_idx, sp.q_val, sp.q_cnt, qc, sp.start,
+                       sp.csc_row, sp.csc_val, lam, one_m_lam, out, G);
   PPS_CHECK_LAUNCH_S("rerank_jaccard_kernel", st);
   return PPS_OK;
 }
 
 size_t rerank_workspace_bytes(int64_t Q, int64_t G, int k1, int k2) {
   // the dense path's size: enough for every call with these shapes
-  return (rr_od_bytes(false, false, Q, G, k1 + 1) + 255) / 256 * 256 + rr_rest_bytes(Q, G, k1, k2);
+  const RrLayout L(k1, k2);
+  return RrCarve(Q + G, L, rr_od_bytes(false, false, Q, G, L.K1), 0).total;
 }
 
 size_t rerank_workspace_bytes_for(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq,
                                   const float* gg, int64_t ldgg, int64_t Q, int64_t G, int k1,
                                   int k2, int flags) {
-  // the OD region's base is 256-B aligned: any such pointer stands in for it
-  float* od_probe = reinterpret_cast<float*>((uintptr_t)256);
-  const bool inplace = rr_inplace(qg, ldqg, qq, ldqq, gg, ldgg, Q, G, k1 + 1, flags, od_probe);
-  const size_t odb = rr_od_bytes(inplace, (flags & PPS_RERANK_WHOLE) != 0, Q, G, k1 + 1);
-  return (odb + 255) / 256 * 256 + rr_rest_bytes(Q, G, k1, k2);
+  bool inplace;
+  return rr_dense_carve(RrIn{qg, qq, gg, ldqg, ldqq, ldgg}, Q, G, RrLayout(k1, k2), flags,
+                        reinterpret_cast<void*>((uintptr_t)256), inplace).total;
 }
 
 // ---- row form --------------------------------------------------
-// The carves of a row-form call: everything is per row of x (about 27 KB at
-// k1 = 20, k2 = 6), plus the fused search's workspace on the features path --
-// nothing grows with N^2.
-struct RrRowsCarve {
-  size_t rowmax, topv, rank, v_idx, v_val, v_cnt, q_idx, q_val, q_cnt, col_cnt, start, fill,
-      csc_row, csc_val, ovf_rows, ovf_n, search, total;
-  int64_t search_bytes;
-  RrRowsCarve(bool features, int64_t Q, int64_t G, int k1, int k2, int segments) {
-    const int64_t N = Q + G;
-    const RrLayout L(k1, k2);
-    const size_t K1 = L.K1, vcap = L.vcap, qcap = L.qcap;
-    size_t p = 0;
-    auto take = [&](size_t bytes) {
-      const size_t r = p;
-      p += (bytes + 255) / 256 * 256;
-      return r;
-    };
-    rowmax = take(4 * N);
-    topv = take(4 * N * K1);
-    rank = take(4 * N * K1);
-    v_idx = take(4 * N * vcap);
-    v_val = take(4 * N * vcap);
-    v_cnt = take(4 * N);
-    q_idx = take(4 * N * qcap);
-    q_val = take(4 * N * qcap);
-    q_cnt = take(4 * N);
-    col_cnt = take(4 * (N + 1));
-    start = take(4 * (N + 1));
-    fill = take(4 * (N + 1));
-    csc_row = take(4 * N * qcap);
-    csc_val = take(4 * N * qcap);
-    ovf_rows = take(4 * N);
-    ovf_n = take(4);
-    search_bytes = features ? search_h2_self_workspace_bound(N, L.K1, segments) : 0;
-    search = take((size_t)search_bytes);
-    total = p;
-  }
-};
+// The carve of a row-form call: everything is per row of x (about 27 KB at
+// k1 = 20, k2 = 6), plus the fused search's workspace as the tail on the
+// features path -- nothing grows with N^2.
+static RrCarve rr_rows_carve(bool features, int64_t N, const RrLayout& L, int segments) {
+  return RrCarve(N, L, 0,
+                 features ? (size_t)search_h2_self_workspace_bound(N, L.K1, segments) : 0);
+}
 
 int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1, int k2,
                                     int segments) {
-  return (int64_t)RrRowsCarve(features, Q, G, k1, k2, segments).total;
+  return (int64_t)rr_rows_carve(features, Q + G, RrLayout(k1, k2), segments).total;
 }
 
 // The stages every row-form pipeline runs the same way, from rank (and, for the
@@ -1207,40 +1197,32 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
   const RrLayout L(k1, k2);
   const int K1 = L.K1, vcap = L.vcap;
   const bool features = src.W == nullptr;
-  const RrRowsCarve C(features, Q, G, k1, k2, src.segments);
+  const RrCarve C = rr_rows_carve(features, N, L, src.segments);
   if (C.total > ws_bytes) {
     set_error("row-form rerank workspace too small: need " + std::to_string(C.total) + " bytes");
     return PPS_ERR_CAPACITY;
   }
-  char* base = reinterpret_cast<char*>(ws);
-  auto f32 = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
-  auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
-  float* rowmax = f32(C.rowmax);
-  float* topv = f32(C.topv);
-  const RrSparse sp{i32(C.rank), i32(C.v_idx), f32(C.v_val), i32(C.v_cnt), i32(C.q_idx),
-                    f32(C.q_val), i32(C.q_cnt), i32(C.col_cnt), i32(C.start), i32(C.fill),
-                    i32(C.csc_row), f32(C.csc_val), i32(C.ovf_rows), i32(C.ovf_n)};
+  const RrCarve::Bound bound = C.bind(ws);
+  const RrSparse& sp = bound.sp;
+  float* rowmax = bound.rowmax;
   // 1-2) rowmax[i] = max_j fl(W[i][j]^2) and the stable (W[i][j], j) top-(k1+1)
   if (features) {
-    const int rc = search_h2_tiled("pps_re_ranking_features", false, src.x2t, N, src.xsq, src.xrs,
-                                   src.x2t, src.xsq, src.xrs, N, src.D, src.metric, K1,
-                                   src.segments, src.tile, base + C.search, C.search_bytes, topv,
-                                   sp.rank, nullptr, nullptr, rowmax, st);
-    if (rc != PPS_OK) return rc;
+    PPS_TRY(search_h2_tiled("pps_re_ranking_features", false, src.x, src.x, src.D, src.metric, K1,
+                            src.segments, src.tile, reinterpret_cast<char*>(ws) + C.tail,
+                            (int64_t)C.tail_bytes, bound.topv, sp.rank, nullptr, nullptr, rowmax,
+                            st));
   } else {
     (void)hipMemsetAsync(rowmax, 0, sizeof(float) * N, st);
     hipLaunchKernelGGL(rerank_rowmax_sq_kernel, dim3((unsigned)N), dim3(256), 0, st, src.W, N,
                        src.ldw, reinterpret_cast<unsigned*>(rowmax));
     PPS_CHECK_LAUNCH_S("rerank_rowmax_sq_kernel", st);
-    const int rc = topk(src.W, N, N, src.ldw, K1, topv, sp.rank, st);
-    if (rc != PPS_OK) return rc;
+    PPS_TRY(topk(src.W, N, N, src.ldw, K1, bound.topv, sp.rank, st));
   }
   // 3) the unique expansion lists, their distances m[i][t], the weights
   PPS_TRY(rr_rows_lists(N, L, sp, st));
   if (features) {
-    const int rc = pair_dist_h2(src.x2t, N, N, src.xsq, src.xrs, src.x2t, src.xsq, src.xrs, N,
-                                src.D, src.metric, sp.v_idx, sp.v_cnt, vcap, sp.v_val, st);
-    if (rc != PPS_OK) return rc;
+    PPS_TRY(pair_dist_h2(src.x, src.x, src.D, src.metric, sp.v_idx, sp.v_cnt, vcap, sp.v_val,
+                         st));
   } else {
     hipLaunchKernelGGL(rerank_gather_w_kernel, dim3((unsigned)N), dim3(64), 0, st, src.W, src.ldw,
                        sp.v_idx, sp.v_cnt, vcap, sp.v_val);
@@ -1250,9 +1232,7 @@ int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double 
   PPS_TRY(rr_rows_weights_vqe(N, L, k2, rowmax, sp, st));
   // 6) out = the q x g block W[i][Q + g]; the Jaccard pass blends it in place
   if (features) {
-    const int rc = distmat_h2_head(src.x2t, Q, N, src.xsq, src.xrs, src.g2t, src.gsq, src.grs, G,
-                                   src.D, src.metric, out, G, st);
-    if (rc != PPS_OK) return rc;
+    PPS_TRY(distmat_h2_head(src.x.head(Q), src.g, src.D, src.metric, out, G, st));
   } else {
     (void)hipMemcpy2DAsync(out, sizeof(float) * G, src.W + Q, sizeof(float) * src.ldw,
                            sizeof(float) * G, Q, hipMemcpyDeviceToDevice, st);
@@ -1271,35 +1251,36 @@ __global__ void rerank_rowmax_join_kernel(float* __restrict__ rowmax, const floa
   rowmax[i] = fmaxf(rowmax[i], i < Q ? rm_q[i] : g_rowmax[i - Q]);
 }
 
-// rerank_rows' per-row carves, then the merge input (two lists [2][N][K1] of
+// rerank_rows' carve (no tail), then the merge input (two lists [2][N][K1] of
 // values and of indices), the query rows' gallery-part maxima and one region
 // the three searches share (they run one after the other on the stream)
 struct RrPreparedCarve {
-  RrRowsCarve rows;
+  RrCarve rows;
   size_t mvals, midx, rm_q, search, total;
   int64_t search_bytes;
-  RrPreparedCarve(int64_t Q, int64_t G, int k1, int k2, int segments)
-      : rows(false, Q, G, k1, k2, 0) {
-    const int64_t N = Q + G, K1 = k1 + 1;
+  RrPreparedCarve(int64_t Q, int64_t G, const RrLayout& L, int segments)
+      : rows(rr_rows_carve(false, Q + G, L, 0)) {
+    const int64_t N = Q + G;
+    const int K1 = L.K1;
     size_t p = rows.total;
     auto take = [&](size_t bytes) {
       const size_t r = p;
-      p += (bytes + 255) / 256 * 256;
+      p += RrCarve::round256(bytes);
       return r;
     };
     mvals = take(4 * 2 * N * K1);
     midx = take(4 * 2 * N * K1);
     rm_q = take(4 * Q);
-    search_bytes = std::max(search_h2_workspace_bound(Q, Q, (int)K1, segments),
-                            std::max(search_h2_workspace_bound(G, Q, (int)K1, segments),
-                                     search_h2_workspace_bound(Q, G, (int)K1, segments)));
+    search_bytes = std::max(search_h2_workspace_bound(Q, Q, K1, segments),
+                            std::max(search_h2_workspace_bound(G, Q, K1, segments),
+                                     search_h2_workspace_bound(Q, G, K1, segments)));
     search = take((size_t)search_bytes);
     total = p;
   }
 };
 
 int64_t rerank_prepared_workspace_bytes(int64_t Q, int64_t G, int k1, int k2, int segments) {
-  return (int64_t)RrPreparedCarve(Q, G, k1, k2, segments).total;
+  return (int64_t)RrPreparedCarve(Q, G, RrLayout(k1, k2), segments).total;
 }
 
 int rerank_prepared(const RrPrepared& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
@@ -1308,35 +1289,30 @@ int rerank_prepared(const RrPrepared& src, int64_t Q, int64_t G, int k1, int k2,
   const int64_t N = Q + G;
   const RrLayout L(k1, k2);
   const int K1 = L.K1, vcap = L.vcap;
-  const RrPreparedCarve P(Q, G, k1, k2, src.segments);
-  const RrRowsCarve& C = P.rows;
+  const RrPreparedCarve P(Q, G, L, src.segments);
   if (P.total > ws_bytes) {
     set_error("prepared rerank workspace too small: need " + std::to_string(P.total) + " bytes");
     return PPS_ERR_CAPACITY;
   }
+  const RrCarve::Bound bound = P.rows.bind(ws);
+  const RrSparse& sp = bound.sp;
+  float* rowmax = bound.rowmax;
   char* base = reinterpret_cast<char*>(ws);
-  auto f32 = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
-  auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
-  float* rowmax = f32(C.rowmax);
-  const RrSparse sp{i32(C.rank), i32(C.v_idx), f32(C.v_val), i32(C.v_cnt), i32(C.q_idx),
-                    f32(C.q_val), i32(C.q_cnt), i32(C.col_cnt), i32(C.start), i32(C.fill),
-                    i32(C.csc_row), f32(C.csc_val), i32(C.ovf_rows), i32(C.ovf_n)};
   // 1-2) per row the stable top-K1 over the query columns (list 0, global
   // offset 0) and over the gallery columns (list 1, offset Q); their stable
   // merge is the top-K1 over all N columns
-  float* mv = f32(P.mvals);
-  int32_t* mi = i32(P.midx);
+  float* mv = reinterpret_cast<float*>(base + P.mvals);
+  int32_t* mi = reinterpret_cast<int32_t*>(base + P.midx);
+  float* rm_q = reinterpret_cast<float*>(base + P.rm_q);
   const int64_t l1 = N * K1;   // list 1 starts here
-  auto search = [&](const uint16_t* a2t, const float* asq, const float* ars, int64_t A,
-                    const uint16_t* b2t, const float* bsq, const float* brs, int64_t B,
-                    int64_t at, float* rm) {
-    return search_h2_tiled(fn, false, a2t, A, asq, ars, b2t, bsq, brs, B, src.D, src.metric, K1,
-                           src.segments, src.tile, base + P.search, P.search_bytes, mv + at,
-                           mi + at, nullptr, nullptr, rm, st);
+  auto search = [&](const H2Operand& a, const H2Operand& b, int64_t at, float* rm) {
+    return search_h2_tiled(fn, false, a, b, src.D, src.metric, K1, src.segments, src.tile,
+                           base + P.search, P.search_bytes, mv + at, mi + at, nullptr, nullptr, rm,
+                           st);
   };
-  PPS_TRY(search(src.q2t, src.qsq, src.qrs, Q, src.q2t, src.qsq, src.qrs, Q, 0, rowmax));
-  PPS_TRY(search(src.g2t, src.gsq, src.grs, G, src.q2t, src.qsq, src.qrs, Q, Q * K1, rowmax + Q));
-  PPS_TRY(search(src.q2t, src.qsq, src.qrs, Q, src.g2t, src.gsq, src.grs, G, l1, f32(P.rm_q)));
+  PPS_TRY(search(src.q, src.q, 0, rowmax));
+  PPS_TRY(search(src.g, src.q, Q * K1, rowmax + Q));
+  PPS_TRY(search(src.q, src.g, l1, rm_q));
   // the gallery rows' gallery-column lists: the first K1 of each prepared row
   (void)hipMemcpy2DAsync(mv + l1 + Q * K1, sizeof(float) * K1, src.nn_vals,
                          sizeof(float) * src.nn_ld, sizeof(float) * K1, G,
@@ -1346,23 +1322,20 @@ int rerank_prepared(const RrPrepared& src, int64_t Q, int64_t G, int k1, int k2,
                          hipMemcpyDeviceToDevice, st);
   MergeOffsets offs{};
   offs.off[1] = Q;
-  PPS_TRY(topk_merge(mv, mi, 2, N, K1, offs, K1, f32(C.topv), sp.rank, st));
+  PPS_TRY(topk_merge(mv, mi, 2, N, K1, offs, K1, bound.topv, sp.rank, st));
   hipLaunchKernelGGL(rerank_rowmax_join_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st,
-                     rowmax, f32(P.rm_q), src.g_rowmax, Q, N);
+                     rowmax, rm_q, src.g_rowmax, Q, N);
   PPS_CHECK_LAUNCH_S("rerank_rowmax_join_kernel", st);
   // 3) the expansion lists name columns of [queries; gallery]: two-part pair
   // distances, the query rows then the gallery rows
   PPS_TRY(rr_rows_lists(N, L, sp, st));
-  PPS_TRY(pair_dist_h2_parts(src.q2t, Q, Q, src.qsq, src.qrs, src.q2t, src.qsq, src.qrs, Q,
-                             src.g2t, src.gsq, src.grs, G, src.D, src.metric, sp.v_idx, sp.v_cnt,
-                             vcap, sp.v_val, st));
-  PPS_TRY(pair_dist_h2_parts(src.g2t, G, G, src.gsq, src.grs, src.q2t, src.qsq, src.qrs, Q,
-                             src.g2t, src.gsq, src.grs, G, src.D, src.metric,
-                             sp.v_idx + Q * vcap, sp.v_cnt + Q, vcap, sp.v_val + Q * vcap, st));
+  PPS_TRY(pair_dist_h2_parts(src.q, src.q, src.g, src.D, src.metric, sp.v_idx, sp.v_cnt, vcap,
+                             sp.v_val, st));
+  PPS_TRY(pair_dist_h2_parts(src.g, src.q, src.g, src.D, src.metric, sp.v_idx + Q * vcap,
+                             sp.v_cnt + Q, vcap, sp.v_val + Q * vcap, st));
   PPS_TRY(rr_rows_weights_vqe(N, L, k2, rowmax, sp, st));
   // 6) as rerank_rows
-  PPS_TRY(distmat_h2_head(src.q2t, Q, Q, src.qsq, src.qrs, src.g2t, src.gsq, src.grs, G, src.D,
-                          src.metric, out, G, st));
+  PPS_TRY(distmat_h2_head(src.q, src.g, src.D, src.metric, out, G, st));
   return rr_rows_blend(Q, G, L, k2, lambda, g_window, rowmax, sp, out, st);
 }
 

@@ -68,41 +68,55 @@ inline int64_t fused_segments(int64_t Q, int64_t G, int segments, int BM, int BN
 // the bytes of its two planes
 inline int64_t h2_plane_elems(int64_t rows, int D) { return (rows + 15) / 16 * 16 * D; }
 inline int64_t h2_planes_bytes(int64_t rows, int D) { return 2 * h2_plane_elems(rows, D) * 2; }
-// The first M rows of an a operand whose planes hold Arows rows against the N
-// rows of a b operand (a cell's bits do not depend on the rows around it).
-inline GemmParams h2_params(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
-                            const float* ars, const uint16_t* b2t, int64_t N, const float* bsq,
-                            const float* brs, int D, int metric, float* out = nullptr,
-                            int64_t ldo = 0, int sym = 0) {
+// One operand: the chunk-tiled f16x2 planes of a row set with the rows' squared
+// norms and scales.  head(m) is the first m rows of the same planes (a cell's
+// bits do not depend on the rows around it).
+struct H2Operand {
+  const uint16_t* planes = nullptr;   // [2][plane_rows padded to 16][D]
+  const float* sq = nullptr;          // squared norms
+  const float* rs = nullptr;          // row scales
+  int64_t rows = 0;                   // rows addressed
+  int64_t plane_rows = 0;             // rows the planes hold (>= rows): decides the plane stride
+  H2Operand head(int64_t m) const { return {planes, sq, rs, m, plane_rows}; }
+  bool complete() const { return planes && sq && rs; }
+};
+// an entry point's (planes, norms, scales, rows): the planes hold exactly those rows
+inline H2Operand h2_operand(const uint16_t* planes, const float* sq, const float* rs,
+                            int64_t rows) {
+  return {planes, sq, rs, rows, rows};
+}
+// The rows of a against the rows of b
+inline GemmParams h2_params(const H2Operand& a, const H2Operand& b, int D, int metric,
+                            float* out = nullptr, int64_t ldo = 0, int sym = 0) {
   GemmParams p{};
   p.splitk = 1;
   p.tiled = 3;
-  p.a3 = a2t; p.a_plane = h2_plane_elems(Arows, D);
-  p.a_bytes = (uint32_t)h2_planes_bytes(Arows, D);
-  p.M = (int)M;
-  p.b3 = b2t; p.b_plane = h2_plane_elems(N, D);
-  p.b_bytes = (uint32_t)h2_planes_bytes(N, D);
-  p.Ncol = (int)N;
+  p.a3 = a.planes; p.a_plane = h2_plane_elems(a.plane_rows, D);
+  p.a_bytes = (uint32_t)h2_planes_bytes(a.plane_rows, D);
+  p.M = (int)a.rows;
+  p.b3 = b.planes; p.b_plane = h2_plane_elems(b.plane_rows, D);
+  p.b_bytes = (uint32_t)h2_planes_bytes(b.plane_rows, D);
+  p.Ncol = (int)b.rows;
   p.Kloop = D;
-  p.norm_a = asq; p.norm_b = bsq;
-  p.rs_a = ars; p.rs_b = brs;
+  p.norm_a = a.sq; p.norm_b = b.sq;
+  p.rs_a = a.rs; p.rs_b = b.rs;
   p.out = out; p.ldo = ldo; p.metric = metric; p.sym = sym;
   return p;
 }
-// The checks of two plane operands of Q and G rows (fn: the entry point's
-// name).  The pointers are looked at only when both operands have rows: an
-// entry returns early on an empty one, which may come with null pointers.
-inline int h2_operands_guard(const char* fn, const uint16_t* q2t, int64_t Q, const float* qsq,
-                             const float* qrs, const uint16_t* g2t, const float* gsq,
-                             const float* grs, int64_t G, int D, int metric) {
+// The checks of two operands (fn: the entry point's name).  The pointers are
+// looked at only when both operands have rows: an entry returns early on an
+// empty one, which may come with null pointers.
+inline int h2_operands_guard(const char* fn, const H2Operand& q, const H2Operand& g, int D,
+                             int metric) {
+  const int64_t Q = q.rows, G = g.rows;
   PPS_ENFORCE_AS(fn, Q >= 0 && G >= 0 && D > 0 && D % 32 == 0, "bad shape (D % 32 == 0)");
   PPS_ENFORCE_AS(fn, Q < (1ll << 31), "Q must fit int32");
   PPS_ENFORCE_AS(fn, metric >= 0 && metric <= 2, "unknown metric");
   PPS_ENFORCE_AS(fn, h2_planes_bytes(Q, D) < kMaxBufBytes && h2_planes_bytes(G, D) < kMaxBufBytes,
                  "planes over 2 GiB");
   if (Q == 0 || G == 0) return PPS_OK;
-  PPS_ENFORCE_AS(fn, q2t && qsq && qrs && g2t && gsq && grs, "null pointer");
-  PPS_ENFORCE_AS(fn, aligned16(q2t) && aligned16(g2t), "planes must be 16-byte aligned");
+  PPS_ENFORCE_AS(fn, q.complete() && g.complete(), "null pointer");
+  PPS_ENFORCE_AS(fn, aligned16(q.planes) && aligned16(g.planes), "planes must be 16-byte aligned");
   return PPS_OK;
 }
 // segments / tile of the fused kernels' work list
@@ -121,37 +135,30 @@ __device__ inline int64_t h2_frag_off(int r, int nkc, int slot) {
 }
 // search_h2.hip: the body of pps_search_h2_tiled / _excl / _rowmax (guards
 // included; fn names the entry in its messages; rowmax null = not wanted)
-int search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q, const float* qsq,
-                    const float* qrs, const uint16_t* g2t, const float* gsq, const float* grs,
-                    int64_t G, int D, int metric, int k, int segments, int tile, void* workspace,
-                    int64_t ws_bytes, float* vals, int32_t* idx, const int32_t* q_group,
-                    const int32_t* g_group, float* rowmax, void* stream);
+int search_h2_tiled(const char* fn, bool excl, const H2Operand& q, const H2Operand& g, int D,
+                    int metric, int k, int segments, int tile, void* workspace, int64_t ws_bytes,
+                    float* vals, int32_t* idx, const int32_t* q_group, const int32_t* g_group,
+                    float* rowmax, void* stream);
 // bytes that hold the workspace of a search of N rows against themselves, as a
 // bound that is non-decreasing in N (host arithmetic)
 int64_t search_h2_self_workspace_bound(int64_t N, int k, int segments);
 // search_h2.hip: the same for Q a-rows against G b-rows: at least the search's
 // workspace, non-decreasing in Q and in G
 int64_t search_h2_workspace_bound(int64_t Q, int64_t G, int k, int segments);
-// pair_h2.hip: out[r][t] = distance of a-row r to b-row lists[r][t], t <
-// min(counts[r], cap) (lists / out rows cap apart; counts null = cap each);
-// the a operand is the first Q rows of planes holding Qrows rows
-int pair_dist_h2(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq, const float* qrs,
-                 const uint16_t* g2t, const float* gsq, const float* grs, int64_t G, int D,
-                 int metric, const int32_t* lists, const int32_t* counts, int cap, float* out,
-                 hipStream_t st);
-// pair_h2.hip: pair_dist_h2 with the b-rows in two plane sets: a list index
-// < B0 is that row of the first b operand, any other index row (index - B0) of
-// the second; indices are clamped to [0, B0 + B1)
-int pair_dist_h2_parts(const uint16_t* q2t, int64_t Q, int64_t Qrows, const float* qsq,
-                       const float* qrs, const uint16_t* b0_2t, const float* b0sq,
-                       const float* b0rs, int64_t B0, const uint16_t* b1_2t, const float* b1sq,
-                       const float* b1rs, int64_t B1, int D, int metric, const int32_t* lists,
-                       const int32_t* counts, int cap, float* out, hipStream_t st);
-// pair_h2.hip: the [M, N] block of the first M rows of an a operand holding
-// Arows rows against a whole b operand (pps_distmat_h2_tiled's launch and bits)
-int distmat_h2_head(const uint16_t* a2t, int64_t M, int64_t Arows, const float* asq,
-                    const float* ars, const uint16_t* b2t, const float* bsq, const float* brs,
-                    int64_t N, int D, int metric, float* out, int64_t ldo, hipStream_t st);
+// pair_h2.hip: out[r][t] = distance of q's row r to g's row lists[r][t], t <
+// min(counts[r], cap) (lists / out rows cap apart; counts null = cap each)
+int pair_dist_h2(const H2Operand& q, const H2Operand& g, int D, int metric, const int32_t* lists,
+                 const int32_t* counts, int cap, float* out, hipStream_t st);
+// pair_h2.hip: pair_dist_h2 with the b-rows in two operands: a list index
+// < b0.rows is that row of b0, any other index row (index - b0.rows) of b1;
+// indices are clamped to [0, b0.rows + b1.rows)
+int pair_dist_h2_parts(const H2Operand& q, const H2Operand& b0, const H2Operand& b1, int D,
+                       int metric, const int32_t* lists, const int32_t* counts, int cap,
+                       float* out, hipStream_t st);
+// pair_h2.hip: the [a.rows, b.rows] block of a (often the head of longer
+// planes) against a whole b (pps_distmat_h2_tiled's launch and bits)
+int distmat_h2_head(const H2Operand& a, const H2Operand& b, int D, int metric, float* out,
+                    int64_t ldo, hipStream_t st);
 
 // ---- evaluation counts (eval_counts.hip) ----------------------------------------
 int collect_matches(const float* dist, int64_t Q, int64_t ldd, const int32_t* qcam,
@@ -207,6 +214,27 @@ int sgs_ranks(const int32_t* perm, int64_t G, const int32_t* rows, int64_t nr,
 size_t sgs_groups_lds_bytes(int64_t G, int U);
 
 // ---- re-ranking (rerank.hip) -------------------------------------------------
+// The row capacities of a (k1, k2) configuration: neighbours kept per row
+// (K1), half-size neighbourhoods (Kh), entries of a V row (vcap) and of a V_qe
+// row (qcap)
+struct RrLayout {
+  int K1, Kh, vbound, vcap, qcap;
+  RrLayout(int k1, int k2) {
+    K1 = k1 + 1;
+    Kh = (int)lrint(k1 / 2.0) + 1;  // int(np.around(k1 / 2.)) + 1
+    vbound = K1 + K1 * Kh;
+    vcap = vbound <= 256 ? 256 : (vbound <= 512 ? 512 : 1024);
+    qcap = k2 * vcap;
+  }
+};
+// The limits of that layout (k1 >= 1 checked by the entry, with its own bound)
+inline int rr_layout_guard(const char* fn, int k1, int k2) {
+  PPS_ENFORCE_AS(fn, k2 >= 1 && k2 <= k1 + 1, "k2 must be in [1, k1 + 1]");
+  const RrLayout L(k1, k2);
+  PPS_ENFORCE_AS(fn, L.vbound <= 1024, "expansion bound (k1+1)(round(k1/2)+2) must be <= 1024");
+  PPS_ENFORCE_AS(fn, L.qcap <= 4096, "k2 * V row capacity must be <= 4096");
+  return PPS_OK;
+}
 int rerank(const float* qg, int64_t ldqg, const float* qq, int64_t ldqq, const float* gg,
            int64_t ldgg, int64_t Q, int64_t G, int k1, int k2, double lambda, void* ws,
            size_t ws_bytes, float* out, hipStream_t st, int flags);
@@ -224,10 +252,8 @@ constexpr int kJacMaxWindow = 38400;   // gallery rows of one Jaccard window (tm
 struct RrRows {
   const float* W;            // twin: [N][ldw]; null = the features path
   int64_t ldw;
-  const uint16_t* x2t;       // features: x's planes, norms, scales (N rows)
-  const float* xsq; const float* xrs;
-  const uint16_t* g2t;       // the gallery rows' own planes (rows Q.. of x)
-  const float* gsq; const float* grs;
+  H2Operand x;               // features: x = [queries; gallery] (N rows)
+  H2Operand g;               // the gallery rows' own planes (rows Q.. of x)
   int D, metric, segments, tile;
 };
 int rerank_rows(const RrRows& src, int64_t Q, int64_t G, int k1, int k2, double lambda,
@@ -243,8 +269,7 @@ int64_t rerank_rows_workspace_bytes(bool features, int64_t Q, int64_t G, int k1,
 // pps_search_h2_tiled_rowmax of the gallery against itself, whatever the
 // queries.  Bit for bit rerank_rows on the planes of [queries; gallery].
 struct RrPrepared {
-  const uint16_t* q2t; const float* qsq; const float* qrs;   // Q rows
-  const uint16_t* g2t; const float* gsq; const float* grs;   // G rows
+  H2Operand q, g;            // Q rows, G rows
   const float* nn_vals; const int32_t* nn_idx; int nn_ld;
   const float* g_rowmax;
   int D, metric, segments, tile;

@@ -313,15 +313,14 @@ int64_t pps_search_h2_workspace_bytes(int64_t Q, int64_t G, int k, int segments)
 
 // pps_search_h2_tiled (excl false), pps_search_h2_tiled_excl (excl true) and
 // pps_search_h2_tiled_rowmax (rowmax given, no exclusion)
-int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t Q,
-                         const float* qsq, const float* qrs, const uint16_t* g2t, const float* gsq,
-                         const float* grs, int64_t G, int D, int metric, int k, int segments,
-                         int tile, void* workspace, int64_t ws_bytes, float* vals,
-                         int32_t* idx, const int32_t* q_group, const int32_t* g_group,
-                         float* rowmax, void* stream) {
+int pps::search_h2_tiled(const char* fn, bool excl, const H2Operand& q, const H2Operand& g, int D,
+                         int metric, int k, int segments, int tile, void* workspace,
+                         int64_t ws_bytes, float* vals, int32_t* idx, const int32_t* q_group,
+                         const int32_t* g_group, float* rowmax, void* stream) {
+  const int64_t Q = q.rows, G = g.rows;
   PPS_ENFORCE_AS(fn, vals && idx, "null pointer");
   PPS_ENFORCE_AS(fn, !excl || (q_group && g_group), "null group pointer");
-  PPS_TRY(h2_operands_guard(fn, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D, metric));
+  PPS_TRY(h2_operands_guard(fn, q, g, D, metric));
   PPS_ENFORCE_AS(fn, k >= 1 && k <= kTkwMaxK,
                  "k must be in [1, " + std::to_string(kTkwMaxK) + "]");
   PPS_TRY(fused_plan_guard(fn, segments, tile));
@@ -358,7 +357,7 @@ int pps::search_h2_tiled(const char* fn, bool excl, const uint16_t* q2t, int64_t
   a.rowmax = reinterpret_cast<unsigned*>(rowmax);
   if (rowmax) (void)hipMemsetAsync(rowmax, 0, sizeof(float) * Q, st);   // the atomicMax's zero
 
-  const GemmParams p = h2_params(q2t, Q, Q, qsq, qrs, g2t, G, gsq, grs, D, metric);
+  const GemmParams p = h2_params(q, g, D, metric);
   const int rc = excl ? launch_search_tile<true, false>(tile, p, a, st)
                       : (rowmax ? launch_search_tile<false, true>(tile, p, a, st)
                                 : launch_search_tile<false, false>(tile, p, a, st));
@@ -372,9 +371,9 @@ int pps_search_h2_tiled(const uint16_t* q2t, int64_t Q, const float* qsq, const 
                         const uint16_t* g2t, const float* gsq, const float* grs, int64_t G,
                         int D, int metric, int k, int segments, int tile, void* workspace,
                         int64_t ws_bytes, float* vals, int32_t* idx, void* stream) {
-  return search_h2_tiled("pps_search_h2_tiled", false, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
-                         metric, k, segments, tile, workspace, ws_bytes, vals, idx, nullptr,
-                         nullptr, nullptr, stream);
+  return search_h2_tiled("pps_search_h2_tiled", false, h2_operand(q2t, qsq, qrs, Q),
+                         h2_operand(g2t, gsq, grs, G), D, metric, k, segments, tile, workspace,
+                         ws_bytes, vals, idx, nullptr, nullptr, nullptr, stream);
 }
 
 int pps_search_h2_tiled_rowmax(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
@@ -383,9 +382,9 @@ int pps_search_h2_tiled_rowmax(const uint16_t* q2t, int64_t Q, const float* qsq,
                                int64_t ws_bytes, float* vals, int32_t* idx, float* rowmax,
                                void* stream) {
   PPS_ENFORCE(rowmax, "null pointer");
-  return search_h2_tiled("pps_search_h2_tiled_rowmax", false, q2t, Q, qsq, qrs, g2t, gsq, grs, G,
-                         D, metric, k, segments, tile, workspace, ws_bytes, vals, idx, nullptr,
-                         nullptr, rowmax, stream);
+  return search_h2_tiled("pps_search_h2_tiled_rowmax", false, h2_operand(q2t, qsq, qrs, Q),
+                         h2_operand(g2t, gsq, grs, G), D, metric, k, segments, tile, workspace,
+                         ws_bytes, vals, idx, nullptr, nullptr, rowmax, stream);
 }
 
 int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, const float* qrs,
@@ -393,7 +392,7 @@ int pps_search_h2_tiled_excl(const uint16_t* q2t, int64_t Q, const float* qsq, c
                              int D, int metric, int k, int segments, int tile, void* workspace,
                              int64_t ws_bytes, float* vals, int32_t* idx,
                              const int32_t* q_group, const int32_t* g_group, void* stream) {
-  return search_h2_tiled("pps_search_h2_tiled_excl", true, q2t, Q, qsq, qrs, g2t, gsq, grs, G, D,
-                         metric, k, segments, tile, workspace, ws_bytes, vals, idx, q_group,
-                         g_group, nullptr, stream);
+  return search_h2_tiled("pps_search_h2_tiled_excl", true, h2_operand(q2t, qsq, qrs, Q),
+                         h2_operand(g2t, gsq, grs, G), D, metric, k, segments, tile, workspace,
+                         ws_bytes, vals, idx, q_group, g_group, nullptr, stream);
 }
